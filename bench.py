@@ -24,15 +24,27 @@ lm_head GEMM + loss chunk by chunk, no [tokens, vocab] logits): same FLOPs, same
 global gradient-norm clip (max_grad_norm 1.0, training_args.py:856) and AdamW (`transformers_amd.TamdAdamW(max_grad_norm=1.0)`:
 SURVEY section 8 row f2; `--optimizer torch` = torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW(fused=True) for the A/B).
 
-The default single-GPU headline run also reports, under `secondary`, the other single-GPU configurations of BASELINE.json and
-the training step -- each in its OWN process after the headline's timed region (this same script with `--config bert-base`,
-`--config llava`, `--train-step`), so that nothing they do can take the headline number down; `--no-secondary` skips them.
-
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+A plain run does only what the headline figure needs: set up, warm up, time `--steps` steps, write the outputs of the last
+timed step if `--dump-outputs DIR` is given, print the line.  Everything else the benchmark measures runs only with `--full`:
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
   roofline     -- the dominant kernel family (the MFMA GEMM, csrc/gemm.hip): algorithmic FLOPs of its launches
-                  in the timed region / their summed HIP-event durations, against the 2.5 PFLOP/s dense bf16 peak;
+                  in the timed region / their summed HIP-event durations, against the 2.5 PFLOP/s dense bf16 peak,
+                  with the clock probe of the diagnostic build (`--gemm-timer` selects the event log explicitly);
+  layer_forward -- one decoder layer's forward as a fraction of the MFMA peak;
   cpu_baseline -- the reference's own eager path (pip transformers, byte-identical hot-path files) timed on the
-                  host cores on a bounded sample: one Llama-3-8B decoder layer, batch 1 x seq 4096, bf16.
+                  host cores on a bounded sample: one Llama-3-8B decoder layer, batch 1 x seq 4096, bf16;
+  secondary    -- (single-GPU headline run) the other single-GPU configurations of BASELINE.json and the training step,
+                  each in its OWN process after the headline's timed region (this same script with `--config bert-base`,
+                  `--config llava`, `--train-step`), so that nothing they do can take the headline number down;
+                  `--no-secondary` skips them;
+  ddp          -- (under DDP) the untimed no_sync() steps that price the exposed all-reduce.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step handed its caller as DIR/<name>.npy (float32):
+`loss`, `logits` and, for training steps, `grad.<parameter>` (and `param.<parameter>` after an optimizer step).  Arrays
+larger than their share of a 64 MB budget are written as a fixed, seeded sample of their flattened elements (the same
+positions in every run), so that two builds can be compared output for output on identical inputs.
+
+Prints ONE JSON line on rank 0 (contract in the task statement).
 """
 from __future__ import annotations
 
@@ -498,7 +510,7 @@ def secondary_legs(timeout_s=300, legs=None):
     for name, extra in legs.items():
         t0 = time.perf_counter()
         try:
-            r = subprocess.run([sys.executable, str(Path(__file__).resolve()), "--gpus", "1", "--no-cpu-baseline",
+            r = subprocess.run([sys.executable, str(Path(__file__).resolve()), "--gpus", "1", "--full", "--no-cpu-baseline",
                                 "--no-secondary", *extra], capture_output=True, text=True, timeout=timeout_s)
             lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
             if r.returncode != 0 or not lines:
@@ -520,6 +532,55 @@ def secondary_legs(timeout_s=300, legs=None):
             out[name] = {"error": repr(e)}
         out[name]["leg_wall_s"] = round(time.perf_counter() - t0, 1)
     return out
+
+
+DUMP_BUDGET_BYTES = 64 * 2 ** 20  # the limit for all files of one --dump-outputs directory
+DUMP_PLAN_BYTES = 48 * 2 ** 20    # what the arrays are sized to: logits first, the rest shared by the per-parameter arrays
+DUMP_LOGITS_ELEMS = 1 << 20       # at most 4 MB of the logits
+
+
+def _sample(name, t, k):
+    """float32 copy of `t` on the host: the whole tensor when it has at most k elements, otherwise k of its flattened
+    elements at positions drawn from a generator seeded by `name` alone (sorted; the same positions in every run)."""
+    import zlib
+
+    import torch
+
+    t = t.detach()
+    if t.numel() <= k:
+        return t.float().cpu().numpy()
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+    idx = torch.randint(0, t.numel(), (k,), generator=g).sort().values.to(t.device)
+    return t[torch.unravel_index(idx, t.shape)].float().cpu().numpy()  # (no flattened copy of a strided view)
+
+
+def dump_outputs(out_dir, kept, model):
+    """--dump-outputs: what the last timed step handed its caller -- `kept` holds the step's model output and its gradients
+    (captured before the gradients were dropped) -- as float32 .npy files in `out_dir`, at most DUMP_BUDGET_BYTES in all."""
+    import numpy as np
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {}
+    o = kept.get("out")
+    if getattr(o, "loss", None) is not None:
+        arrays["loss"] = o.loss.detach().float().reshape(1).cpu().numpy()
+    logits = getattr(o, "logits", None)
+    if logits is not None:
+        arrays["logits"] = _sample("logits", logits, DUMP_LOGITS_ELEMS)
+    per_param = [(f"grad.{n}", g) for n, g in kept.get("grads", [])]
+    if kept.get("optimizer_step"):  # a training step's caller receives the updated weights
+        per_param += [(f"param.{n}", p) for n, p in model.named_parameters()]
+    if per_param:
+        left = DUMP_PLAN_BYTES - sum(a.nbytes for a in arrays.values())
+        k = max(left // (4 * len(per_param)), 1)
+        for name, t in per_param:
+            arrays[name] = _sample(name, t, k)
+    total = sum(a.nbytes + 128 for a in arrays.values())  # (+ the .npy header)
+    assert total <= DUMP_BUDGET_BYTES, total
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    return {"dir": str(out_dir), "arrays": len(arrays), "bytes": total}
 
 
 # ------------------------------------------------------------------------------------------------ workloads
@@ -544,8 +605,14 @@ def build_llama(c, dev, args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="number of timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, everything else the benchmark measures: the GEMM roofline and clock "
+                         "probe, one decoder layer's forward, the CPU baseline, the `secondary` legs, the DDP breakdown")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, logits, gradients; a fixed "
+                         "seeded sample of the larger ones) as DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--config", default="llama3-8b", choices=sorted(CONFIGS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--hip-graph", action="store_true",
@@ -553,10 +620,11 @@ def main():
                          "the warm-up and time replays -- for configurations whose host side (hundreds to thousands of "
                          "10-50 us launches) bounds the step")
     ap.add_argument("--fused-lm-head-loss", action="store_true")
-    ap.add_argument("--gemm-timer", choices=("auto", "on", "off"), default="auto",
+    ap.add_argument("--gemm-timer", choices=("auto", "on", "off"), default=None,
                     help="HIP-event pair around every GEMM launch of the timed region (the `roofline` object).  auto = on for "
                          "the Llama configurations, off for bert-base / llava: their steps are hundreds to thousands of "
-                         "10-50 us launches and two event records per GEMM add host time to a host-bound step")
+                         "10-50 us launches and two event records per GEMM add host time to a host-bound step.  "
+                         "Default: auto with --full, off without")
     ap.add_argument("--force-ddp", action="store_true",
                     help="wrap in DDP over RCCL even with one rank (exercises init / bucket all-reduce / destroy)")
     ap.add_argument("--ddp-grads", choices=("none", "zero", "keep"), default=None,
@@ -582,6 +650,12 @@ def main():
                     help="under DDP: skip the untimed no_sync() steps after the timed region that price the exposed all-reduce "
                          "(`ddp.exposed_allreduce_ms`, `ddp.busbw_GBps`)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.gemm_timer is None:
+        args.gemm_timer = "auto" if args.full else "off"
+    if not args.full:
+        args.no_ddp_breakdown = True
 
     launched = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if args.gpus > 1 and not launched:
@@ -711,10 +785,17 @@ def main():
         e1.record()
         opt_events.append((e0, e1))
 
+    # --dump-outputs: the step that runs with `kept["on"]` set leaves its output and gradients here (references taken before
+    # zero_grad drops them: no copy, no extra launch -- unless the gradients are zeroed in place, which only DDP runs do)
+    kept = {"on": False}
+
     def step():
         if not backward:
             with torch.no_grad():
-                return fwd(net).logits[0, -1, 0].float()
+                o = fwd(net)
+                if kept["on"]:
+                    kept["out"] = o
+                return o.logits[0, -1, 0].float()
         out = fwd(net)
         out.loss.backward()
         if opt is not None:
@@ -726,6 +807,10 @@ def main():
         # in place, 1285.8 never zeroed (non-DDP step on the same box: 1273.4).  `--ddp-grads none|zero|keep` overrides.
         # (with the zero-copy hand-over the gradients must be None when the backward starts: the Trainer's default)
         mode = args.ddp_grads or ("zero" if (ddp and args.no_ddp_zero_copy) else "none")
+        if kept["on"]:
+            kept.update(out=out, optimizer_step=opt is not None,
+                        grads=[(n, p.grad.clone() if mode == "zero" else p.grad) for n, p in model.named_parameters()
+                               if p.grad is not None])
         if mode == "none":
             model.zero_grad(set_to_none=True)
         elif mode == "zero":
@@ -767,8 +852,10 @@ def main():
                 step()
         torch.cuda.current_stream().wait_stream(side)
         graph = torch.cuda.CUDAGraph()
+        kept["on"] = args.dump_outputs is not None  # (what the captured step leaves there, every replay rewrites)
         with torch.cuda.graph(graph):
             static_loss = step()
+        kept["on"] = False
 
         def run():
             graph.replay()
@@ -778,11 +865,19 @@ def main():
     transformers_amd.fallback_calls(reset=True)
     timer.enabled = use_timer and rank == 0 and not args.hip_graph  # (per-GEMM events cannot be read out of a replayed graph)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if i == args.steps - 1 and args.dump_outputs is not None and not args.hip_graph:
+            kept["on"] = True
         loss = run()
     barrier()
     dt = time.perf_counter() - t0
     timer.enabled = False
+    kept["on"] = False
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, kept, model)
+    kept.clear()
+    kept["on"] = False
     roofline_steps = args.steps
     if not use_timer and rank == 0 and not args.hip_graph and args.gemm_timer != "off":
         # bert-base / llava: hundreds to thousands of 10-100 us launches per step, where two event records per GEMM would
@@ -850,6 +945,8 @@ def main():
                                        if m.__dict__.get("_tamd_stack", (None, 1))[1] == 0),
             "roofline": roofline,
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if ddp:
             from transformers_amd import ddp as tamd_ddp
 
@@ -871,7 +968,7 @@ def main():
                                       optimizer_hbm_bytes=(1 + 7) * sum(p.numel() * p.element_size() for p in model.parameters()),
                                       grad_norm=(float(opt.grad_norm) if getattr(opt, "grad_norm", None) is not None else None))
             line["train_step"]["optimizer_TBps"] = line["train_step"]["optimizer_hbm_bytes"] / (line["train_step"]["optimizer_ms"] * 1e-3) / 1e12
-        if kind == "llama" and world == 1 and not args.hip_graph and not args.train_step:
+        if args.full and kind == "llama" and world == 1 and not args.hip_graph and not args.train_step:
             # the north star's own number: one decoder layer's forward as a fraction of the MFMA peak (outside the timed region)
             try:
                 fb = dict(transformers_amd.fallback_calls())
@@ -879,21 +976,21 @@ def main():
                 line["layer_forward"]["fallback_calls"] = sum(transformers_amd.fallback_calls().values()) - sum(fb.values())
             except Exception as e:  # diagnostics must never take the headline number down
                 line["layer_forward"] = {"error": repr(e)}
-        if roofline is not None and world == 1 and args.config == "llama3-8b":
+        if args.full and roofline is not None and world == 1 and args.config == "llama3-8b":
             try:
                 roofline["clock_probe"] = clock_probe(dev)
                 if "ms" in line.get("layer_forward", {}):
                     line["layer_forward"]["clock_GHz"] = roofline["clock_probe"]["clock_GHz"]
             except Exception as e:  # diagnostics only
                 roofline["clock_probe"] = {"error": repr(e)}
-        if not args.no_cpu_baseline and world == 1 and args.config in ("llama3-8b", "bert-base"):
+        if args.full and not args.no_cpu_baseline and world == 1 and args.config in ("llama3-8b", "bert-base"):
             try:
                 line["cpu_baseline"] = (cpu_baseline(c["model"], seq, c["model"]["num_hidden_layers"])
                                         if kind == "llama" else cpu_baseline_bert(batch, seq))
             except Exception as e:  # the baseline leg must never take the GPU number down with it
                 line["cpu_baseline"] = {"error": repr(e)}
-        if (world == 1 and args.config == "llama3-8b" and not args.no_secondary and not args.train_step and not args.hip_graph
-                and not ddp):
+        if (args.full and world == 1 and args.config == "llama3-8b" and not args.no_secondary and not args.train_step
+                and not args.hip_graph and not ddp):
             # BASELINE configs 2 and 5 + the end-to-end training step, each in its own process (this one frees its memory first)
             try:
                 import gc

@@ -311,7 +311,7 @@ def test_bench_ddp_path_over_rccl_world1():
     """the RCCL path had never executed.  `bench.py --force-ddp` at world size 1: process-group init over
     RCCL ("nccl" on ROCm), DDP wrap of the accelerated model (fused-weight views, bucket views of the gradients),
     bucketed all-reduce overlapped with the backward of the custom ops, destroy -- and the same loss as without DDP."""
-    base = [sys.executable, "bench.py", "--config", "llama-tiny", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"]
+    base = [sys.executable, "bench.py", "--config", "llama-tiny", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--full"]
     plain = _run(base)
     ddp = _run(base + ["--force-ddp", "--verify-ddp"])
     assert "DDP over RCCL" in ddp["config"]["parallelism"] and ddp["n_gpus"] == 1

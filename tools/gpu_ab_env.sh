@@ -8,7 +8,7 @@ out=$PWD/gpurun_out
 mkdir -p $out
 export PYTHONUNBUFFERED=1 TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 for arm in "$a" "$b" "$a" "$b"; do
-  env $var=$arm timeout 400 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary "$@" 2>> $out/${tag}_ab.err |
+  env $var=$arm timeout 400 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --full "$@" 2>> $out/${tag}_ab.err |
     grep -m1 '^{"metric' | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())

@@ -37,7 +37,7 @@ step_smoke() {
   tail -3 $out/${tag}_smoke.log
 }
 step_bench() {
-  timeout 900 python bench.py "$@" > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+  timeout 900 python bench.py --full "$@" > $out/${tag}_bench.json 2> $out/${tag}_bench.err
   echo "bench exit $?"; cut -c1-400 $out/${tag}_bench.json; tail -2 $out/${tag}_bench.err
   python - <<PY
 import json
@@ -52,9 +52,9 @@ PY
 step_bench_fast() { step_bench --no-cpu-baseline "$@"; }
 step_prof() {
   cd /tmp
-  timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $out/$tag/stats -o bench -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $out/${tag}_prof_bench.log 2>&1
-  timeout 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/$tag/fetch -o bench -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline > $out/${tag}_pmc_fetch.log 2>&1
-  timeout 240 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/$tag/write -o bench -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline > $out/${tag}_pmc_write.log 2>&1
+  timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $out/$tag/stats -o bench -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --full > $out/${tag}_prof_bench.log 2>&1
+  timeout 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/$tag/fetch -o bench -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --full > $out/${tag}_pmc_fetch.log 2>&1
+  timeout 240 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/$tag/write -o bench -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --full > $out/${tag}_pmc_write.log 2>&1
   cd $R
   python tools/prof_traffic.py $out/$tag $out/${tag} $round > $out/${tag}_traffic.log 2>&1
   cp $(find $out/$tag/stats -name "*kernel_stats.csv" | head -1) $out/${tag}_bench_kernel_stats.csv 2>/dev/null
@@ -120,7 +120,7 @@ step_attn_prof() {
 bench_line() {  # <file suffix> <bench.py args...>
   local name=$1
   shift
-  timeout 300 python bench.py "$@" 2> $out/${tag}_bench_${name}.err | grep -m1 '^{"metric' | tee -a $out/${tag}_bench_${name}.jsonl | cut -c1-330
+  timeout 300 python bench.py --full "$@" 2> $out/${tag}_bench_${name}.err | grep -m1 '^{"metric' | tee -a $out/${tag}_bench_${name}.jsonl | cut -c1-330
 }
 step_prof_cfg() {  # rocprofv3 kernel stats of one of the other BASELINE configurations: prof_cfg bb | lv  (bert-base | llava)
   local cfg=$1
@@ -147,7 +147,7 @@ step_ddp2() {
   n=$(python -c "import torch; print(torch.cuda.device_count())")
   if [ "$n" -ge 2 ]; then
     for arm in "--verify-ddp" "--no-ddp-zero-copy"; do
-      timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 3 --no-cpu-baseline $arm 2>> $out/${tag}_bench_n2.err | grep -m1 '^{"metric' >> $out/${tag}_bench_n2.jsonl
+      timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 3 --no-cpu-baseline --full $arm 2>> $out/${tag}_bench_n2.err | grep -m1 '^{"metric' >> $out/${tag}_bench_n2.jsonl
     done
     cut -c1-300 $out/${tag}_bench_n2.jsonl
   else
