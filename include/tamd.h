@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define TAMD_ABI_VERSION 11
+#define TAMD_ABI_VERSION 12
 
 typedef void* tamd_stream_t; /* hipStream_t */
 
@@ -442,6 +442,30 @@ int tamd_mt_scale(const int64_t* table, int n_tensors, int64_t total_chunks, con
 int tamd_mt_adamw_step(const int64_t* table, int n_tensors, int64_t total_chunks, double lr, double beta1, double beta2,
                        double eps, double weight_decay, int64_t step, double grad_scale, const float* grad_scale_dev,
                        int dtype, int state_dtype, tamd_stream_t stream);
+
+/* ---- stochastic rounding of bf16 parameters (ABI 12; csrc/sround.h has the definitions in full) ----
+ * A bf16 weight of magnitude 0.02 has an ulp of 2^-13; an AdamW step at lr = 2e-5 is a sixth of it, and round-to-nearest
+ * puts the weight back where it was on every step.  sr_bf16(x, r16) = (bits(x) + r16) >> 16 for finite x (inf / NaN: the
+ * round-to-nearest conversion) rounds away from zero with probability (low 16 bits of x) / 65536: the expected stored
+ * value is the fp32 value, values that are already bf16 never move, and a finite x within the last ulp below the largest
+ * bf16 may round to inf.  r16 = tamd_sr_bits(key, step, index) is a counter-based hash -- a pure function of the tensor's
+ * 64-bit key, its optimizer step count and the element's index inside the tensor, whichever workgroup, chunk, table slot or
+ * vector / scalar path handles the element.  The key of a parameter is attn_seed_mix(seed + ordinal) mod 2^64 (splitmix64's
+ * finaliser, csrc/dropout.h; transformers_amd.ops.sr_key): seed = the optimizer's 63-bit seed, ordinal = the parameter's
+ * position across all param_groups. */
+uint32_t tamd_sr_bits(uint64_t key, uint64_t step, uint64_t index);
+/* y[i] = sr_bf16(x[i], tamd_sr_bits(key, step, i)), i in [0, n): an fp32 tensor cast down without bias.  No alignment
+ * requirement (16-byte accesses when both pointers are 16-byte aligned, one element per lane otherwise). */
+int tamd_sr_round(const float* x, void* y_bf16, int64_t n, uint64_t key, uint64_t step, tamd_stream_t stream);
+/* tamd_mt_adamw_step for bf16 parameters and gradients, the parameter stored through sr_bf16 with
+ * r16 = tamd_sr_bits(key[i], step, element index); the moments (state_dtype TAMD_BF16 or TAMD_F32, TAMD_E_DTYPE otherwise)
+ * are stored round-to-nearest as before.  The table carries one more column after the words of the plain table:
+ *     [6n+1, 7n+1) key of tensor i          (7n + 1 words)
+ * Same arithmetic as tamd_mt_adamw_step, operation for operation: the stored parameter equals sr_bf16 of the fp32 value
+ * that the fp32 kernel computes from the same inputs. */
+int tamd_mt_adamw_step_sr(const int64_t* table, int n_tensors, int64_t total_chunks, double lr, double beta1, double beta2,
+                          double eps, double weight_decay, int64_t step, double grad_scale, const float* grad_scale_dev,
+                          int state_dtype, tamd_stream_t stream);
 
 #ifdef __cplusplus
 }

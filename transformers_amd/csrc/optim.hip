@@ -14,6 +14,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "sround.h"
 
 namespace tamd {
 
@@ -299,6 +300,96 @@ __global__ __launch_bounds__(kMtThreads) void mt_adamw_kernel(const int64_t* __r
   }
 }
 
+// ---- stochastic rounding of bf16 parameters (sround.h).  mt_adamw_kernel<bf16_t, S> with the parameter stored through sr_bf16:
+// the random bits of element i of tensor t at step `step` are sr_bits(key[t], step, i), key = table words [6n+1, 7n+1) -- a
+// function of the element, not of the chunk, the slot or the path (vector body / one-element tail) that handles it.  Chunks
+// start at multiples of 64 Ki elements and a vector at a multiple of VE, so a vector covers whole element pairs: one hash
+// (three 32-bit multiplies) per pair.  The moments move by more than an ulp per step and are stored round-to-nearest.
+template <typename S>
+__global__ __launch_bounds__(kMtThreads) void mt_adamw_sr_kernel(const int64_t* __restrict__ table, int n, float decay, float b1,
+                                                                 float b2, float step_size, float inv_bc2_sqrt, float eps,
+                                                                 float grad_scale, const float* __restrict__ grad_scale_dev,
+                                                                 unsigned long long step) {
+  typedef bf16_t T;
+  constexpr int VE = vec16<T>::N < vec16<S>::N ? vec16<T>::N : vec16<S>::N;
+  const MtSlot s = mt_slot(table, n, blockIdx.x);
+  if (s.count <= 0) return;
+  const int64_t nn = n;
+  T* p = reinterpret_cast<T*>(table[s.tensor]) + s.first;
+  const T* g = reinterpret_cast<const T*>(table[nn + s.tensor]) + s.first;
+  S* m = reinterpret_cast<S*>(table[2 * nn + s.tensor]) + s.first;
+  S* v = reinterpret_cast<S*>(table[3 * nn + s.tensor]) + s.first;
+  const unsigned long long stream = sr_stream((unsigned long long)table[6 * nn + 1 + s.tensor], step);
+  const float gs = grad_scale_dev != nullptr ? grad_scale * *grad_scale_dev : grad_scale;
+  const uintptr_t mis = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                        reinterpret_cast<uintptr_t>(v);
+  const int64_t n_vec = (mis & 15u) == 0 ? s.count - s.count % VE : 0;
+  for (int64_t idx = (int64_t)threadIdx.x * VE; idx < n_vec; idx += (int64_t)kMtThreads * VE) {
+    float pp[VE], gg[VE], mm[VE], vv[VE];
+    load_vec<T, VE>(p + idx, pp);
+    load_vec<T, VE>(g + idx, gg);
+    load_vec<S, VE>(m + idx, mm);
+    load_vec<S, VE>(v + idx, vv);
+#pragma unroll
+    for (int i = 0; i < VE; ++i) {  // (the arithmetic of adamw_kernel, operation for operation)
+      const float gi = gg[i] * gs;
+      const float pd = pp[i] * decay;
+      const float mn = mm[i] + (1.f - b1) * (gi - mm[i]);
+      const float vn = b2 * vv[i] + (1.f - b2) * gi * gi;
+      const float denom = sqrtf(vn) * inv_bc2_sqrt + eps;
+      pp[i] = pd - step_size * (mn / denom);
+      mm[i] = mn;
+      vv[i] = vn;
+    }
+    const unsigned long long pair0 = (unsigned long long)(s.first + idx) >> 1;  // s.first + idx is a multiple of VE
+    unsigned int pw[VE / 2];
+#pragma unroll
+    for (int i = 0; i < VE / 2; ++i) pw[i] = sr_pack2_bf16(pp[2 * i], pp[2 * i + 1], sr_pair_word(stream, pair0 + i));
+    if constexpr (VE == 8) {
+      st16(p + idx, u32x4{pw[0], pw[1], pw[2], pw[3]});
+    } else {
+      st8(p + idx, u32x2{pw[0], pw[1]});
+    }
+    store_vec<S, VE>(m + idx, mm);
+    store_vec<S, VE>(v + idx, vv);
+  }
+  for (int64_t idx = n_vec + threadIdx.x; idx < s.count; idx += kMtThreads) {
+    const float gi = load1(g + idx) * gs;
+    const float pd = load1(p + idx) * decay;
+    const float m0 = load1(m + idx), v0 = load1(v + idx);
+    const float mn = m0 + (1.f - b1) * (gi - m0);
+    const float vn = b2 * v0 + (1.f - b2) * gi * gi;
+    const float denom = sqrtf(vn) * inv_bc2_sqrt + eps;
+    const unsigned long long i = (unsigned long long)(s.first + idx);
+    const unsigned w = sr_pair_word(stream, i >> 1);
+    p[idx].bits = sr_bf16(pd - step_size * (mn / denom), (i & 1) ? (w >> 16) : (w & 0xffffu));
+    store1(m + idx, mn);
+    store1(v + idx, vn);
+  }
+}
+
+// y[i] = sr_bf16(x[i], sr_bits(key, step, i)): eight elements per lane (two 16-byte loads, one 16-byte store) while both
+// pointers are 16-byte aligned, one element per lane for the rest -- the same bits either way
+__global__ __launch_bounds__(256) void sr_round_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, int64_t n_vec,
+                                                       int64_t n, unsigned long long key, unsigned long long step) {
+  const unsigned long long stream = sr_stream(key, step);
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t idx = tid * 8; idx < n_vec; idx += stride * 8) {
+    float xx[8];
+    unpack16<float>(ld16(x + idx), xx);
+    unpack16<float>(ld16(x + idx + 4), xx + 4);
+    const unsigned long long pair0 = (unsigned long long)idx >> 1;
+    u32x4 out;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) out[i] = sr_pack2_bf16(xx[2 * i], xx[2 * i + 1], sr_pair_word(stream, pair0 + i));
+    st16(y + idx, out);
+  }
+  for (int64_t idx = n_vec + tid; idx < n; idx += stride) {
+    const unsigned w = sr_pair_word(stream, (unsigned long long)idx >> 1);
+    y[idx].bits = sr_bf16(x[idx], (idx & 1) ? (w >> 16) : (w & 0xffffu));
+  }
+}
+
 }  // namespace tamd
 
 using namespace tamd;
@@ -381,4 +472,42 @@ extern "C" int tamd_mt_adamw_step(const int64_t* table, int n_tensors, int64_t t
   if (dtype == TAMD_F32 && state_dtype == TAMD_F32) TAMD_MT_ADAMW(float, float);
 #undef TAMD_MT_ADAMW
   return TAMD_E_DTYPE;
+}
+
+extern "C" uint32_t tamd_sr_bits(uint64_t key, uint64_t step, uint64_t index) { return sr_bits(key, step, index); }
+
+extern "C" int tamd_sr_round(const float* x, void* y_bf16, int64_t n, uint64_t key, uint64_t step, tamd_stream_t stream) {
+  if (n < 0) return TAMD_E_ARG;
+  if (n == 0) return TAMD_OK;
+  if (!x || !y_bf16) return TAMD_E_NULL;
+  const int64_t n_vec = aligned16(x) && aligned16(y_bf16) ? n - n % 8 : 0;
+  int64_t blocks = ceil_div(n_vec > 0 ? n_vec / 8 : n, 256);
+  if (blocks > 256 * 16) blocks = 256 * 16;  // grid-stride beyond 16 workgroups per CU
+  hipLaunchKernelGGL(sr_round_kernel, dim3((unsigned)blocks), dim3(256), 0, TAMD_STREAM(stream), x, (bf16_t*)y_bf16, n_vec, n,
+                     (unsigned long long)key, (unsigned long long)step);
+  return launch_status();
+}
+
+extern "C" int tamd_mt_adamw_step_sr(const int64_t* table, int n_tensors, int64_t total_chunks, double lr, double beta1,
+                                     double beta2, double eps, double weight_decay, int64_t step, double grad_scale,
+                                     const float* grad_scale_dev, int state_dtype, tamd_stream_t stream) {
+  if (n_tensors <= 0 || total_chunks <= 0) return TAMD_OK;
+  if (!table) return TAMD_E_NULL;
+  if (total_chunks > 0x7fffffffLL) return TAMD_E_ARG;
+  if (step < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return TAMD_E_ARG;
+  if (state_dtype != TAMD_BF16 && state_dtype != TAMD_F32) return TAMD_E_DTYPE;
+  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  const float step_size = (float)(lr / bc1), inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+  const float decay = (float)(1.0 - lr * weight_decay);
+  hipStream_t s = TAMD_STREAM(stream);
+#define TAMD_MT_ADAMW_SR(S_)                                                                                            \
+  hipLaunchKernelGGL((mt_adamw_sr_kernel<S_>), dim3((unsigned)total_chunks), dim3(kMtThreads), 0, s, table, n_tensors, \
+                     decay, (float)beta1, (float)beta2, step_size, inv_bc2_sqrt, (float)eps, (float)grad_scale,        \
+                     grad_scale_dev, (unsigned long long)step)
+  if (state_dtype == TAMD_BF16)
+    TAMD_MT_ADAMW_SR(bf16_t);
+  else
+    TAMD_MT_ADAMW_SR(float);
+#undef TAMD_MT_ADAMW_SR
+  return launch_status();
 }

@@ -41,7 +41,7 @@ using OptTensor = std::optional<at::Tensor>;
   X(tamd_layernorm_fwd) X(tamd_layernorm_bwd) X(tamd_layernorm_dropout_fwd) X(tamd_layernorm_dropout_bwd)             \
   X(tamd_rope_inplace) X(tamd_embedding_fwd) X(tamd_embedding_bwd_workspace_bytes) X(tamd_embedding_bwd)              \
   X(tamd_bert_embeddings_fwd) X(tamd_swiglu_fwd) X(tamd_swiglu_bwd) X(tamd_bias_act_fwd) X(tamd_bias_act_bwd)         \
-  X(tamd_add) X(tamd_adamw_step) X(tamd_mt_sumsq) X(tamd_mt_norm_finish) X(tamd_mt_scale) X(tamd_mt_adamw_step) X(tamd_colsum_workspace_bytes) X(tamd_colsum) X(tamd_transpose)                      \
+  X(tamd_add) X(tamd_adamw_step) X(tamd_mt_sumsq) X(tamd_mt_norm_finish) X(tamd_mt_scale) X(tamd_mt_adamw_step) X(tamd_sr_bits) X(tamd_sr_round) X(tamd_mt_adamw_step_sr) X(tamd_colsum_workspace_bytes) X(tamd_colsum) X(tamd_transpose)                      \
   X(tamd_cross_entropy_fwd) X(tamd_cross_entropy_bwd) X(tamd_gemm) X(tamd_gemm_workspace_bytes) X(tamd_gemm_ws)       \
   X(tamd_gemm_swiglu) X(tamd_gemm_swiglu_bwd) X(tamd_gemm_colscale) X(tamd_gemm_seg) X(tamd_gemm_group_workspace_bytes) X(tamd_gemm_group) X(tamd_attn_fwd) X(tamd_attn_bwd)   \
   X(tamd_attn_decode_workspace_bytes) X(tamd_attn_decode)
@@ -474,6 +474,32 @@ void k_mt_adamw_step_(const Tensor& table, int64_t n_tensors, int64_t total_chun
                                  weight_decay, step, grad_scale, (const float*)ptr(grad_scale_dev), (int)dtype,
                                  (int)state_dtype, L.stream),
         "tamd_mt_adamw_step");
+}
+// ---- stochastic rounding (include/tamd.h "stochastic rounding of bf16 parameters"): `key` is the tensor's 64-bit word as
+// the int64 of the same bits
+Tensor k_sr_round_bf16(const Tensor& x_, int64_t key, int64_t step) {
+  TORCH_CHECK(x_.scalar_type() == at::kFloat, "tamd: sr_round_bf16 takes an fp32 tensor, got ", x_.scalar_type());
+  TORCH_CHECK(step >= 0, "tamd: sr_round_bf16 step must be >= 0");
+  Tensor x = contig(x_);
+  Launch L({&x});
+  Tensor y = at::empty(x.sizes(), x.options().dtype(at::kBFloat16));
+  check(api().tamd_sr_round((const float*)ptr(x), mptr(y), x.numel(), (uint64_t)key, (uint64_t)step, L.stream), "tamd_sr_round");
+  return y;
+}
+void k_mt_adamw_step_sr_(const Tensor& table, int64_t n_tensors, int64_t total_chunks, double lr, double beta1, double beta2,
+                         double eps, double weight_decay, int64_t step, double grad_scale, const OptTensor& grad_scale_dev,
+                         int64_t state_dtype) {
+  check_mt_table(table, n_tensors, total_chunks);
+  TORCH_CHECK(table.numel() >= 7 * n_tensors + 1,
+              "tamd: mt_adamw_step_sr_ needs the table with the key column (7 * n_tensors + 1 words)");
+  if (grad_scale_dev.has_value() && grad_scale_dev->defined())
+    TORCH_CHECK(grad_scale_dev->scalar_type() == at::kFloat && grad_scale_dev->numel() >= 1,
+                "tamd: mt_adamw_step_sr_ grad_scale_dev must be an fp32 scalar in device memory");
+  Launch L({&table, p(grad_scale_dev)});
+  check(api().tamd_mt_adamw_step_sr((const int64_t*)ptr(table), (int)n_tensors, total_chunks, lr, beta1, beta2, eps,
+                                    weight_decay, step, grad_scale, (const float*)ptr(grad_scale_dev), (int)state_dtype,
+                                    L.stream),
+        "tamd_mt_adamw_step_sr");
 }
 
 Tensor k_colsum(const Tensor& x2d) {
@@ -1581,6 +1607,9 @@ TORCH_LIBRARY(tamd, m) {
   m.def("mt_scale_(Tensor table, int n_tensors, int total_chunks, Tensor coef, int dtype) -> ()");
   m.def("mt_adamw_step_(Tensor table, int n_tensors, int total_chunks, float lr, float beta1, float beta2, float eps, "
         "float weight_decay, int step, float grad_scale, Tensor? grad_scale_dev, int dtype, int state_dtype) -> ()");
+  m.def("mt_adamw_step_sr_(Tensor table, int n_tensors, int total_chunks, float lr, float beta1, float beta2, float eps, "
+        "float weight_decay, int step, float grad_scale, Tensor? grad_scale_dev, int state_dtype) -> ()");
+  m.def("sr_round_bf16(Tensor x, int key, int step) -> Tensor");
   m.def("gemm(Tensor a, Tensor b, bool a_km=False, bool b_kn=False, Tensor? bias=None, Tensor? residual=None, "
         "int epilogue=0, int act=0, int sched=0) -> Tensor");
   m.def("gemm_out(Tensor(a!) out, Tensor a, Tensor b, bool a_km=False, bool b_kn=False, Tensor? bias=None, "
@@ -1675,6 +1704,8 @@ TORCH_LIBRARY(tamd, m) {
   m.impl("mt_norm_finish", &k_mt_norm_finish);                       \
   m.impl("mt_scale_", &k_mt_scale_);                                 \
   m.impl("mt_adamw_step_", &k_mt_adamw_step_);                       \
+  m.impl("mt_adamw_step_sr_", &k_mt_adamw_step_sr_);                 \
+  m.impl("sr_round_bf16", &k_sr_round_bf16);                         \
   m.impl("gemm", &op_gemm);                                          \
   m.impl("gemm_out", &op_gemm_out);                                  \
   m.impl("gemm_swiglu", &op_gemm_swiglu);                            \

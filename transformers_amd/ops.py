@@ -391,6 +391,10 @@ register("mt_norm_finish", lambda partials, out, max_norm: None)
 register("mt_scale_", lambda table, n_tensors, total_chunks, coef, dtype: None)
 register("mt_adamw_step_", lambda table, n_tensors, total_chunks, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
                                   grad_scale_dev, dtype, state_dtype: None)
+register("mt_adamw_step_sr_", lambda table, n_tensors, total_chunks, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
+                                     grad_scale_dev, state_dtype: None)
+register("sr_round_bf16", lambda x, key, step: torch.empty_like(x, dtype=torch.bfloat16,
+                                                                memory_format=torch.contiguous_format))
 
 
 def _gemm_shape(a, b, a_km, b_kn):
@@ -847,6 +851,26 @@ def hidden_dropout_keep_mask(seed: int, rows: int, cols: int, p: float) -> torch
         x ^= x >> np.uint32(16)
     thr = np.uint32(min(4294967295.0, float(np.float32(p)) * 4294967296.0))
     return torch.from_numpy((x >= thr).reshape(rows, cols))
+
+
+def sr_key(seed: int, ordinal: int = 0) -> int:
+    """The 64-bit stochastic-rounding key of parameter `ordinal` (its position across all param_groups) under the 63-bit
+    `seed`: attn_seed_mix(seed + ordinal) mod 2^64, splitmix64's finaliser (csrc/sround.h `sr_key`, csrc/dropout.h) -- as the
+    SIGNED int64 of the same bits, which is how the dispatcher ops and the multi-tensor table carry it."""
+    m = (1 << 64) - 1
+    z = (int(seed) + int(ordinal)) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    z ^= z >> 31
+    return z - (1 << 64) if z >> 63 else z
+
+
+def sr_round_bf16(x, seed, step=0, ordinal=0):
+    """fp32 -> bf16 by stochastic rounding (csrc/sround.h): x rounds away from zero with probability (low 16 bits) / 65536, so
+    the expected result is x; values that are already bf16 do not move.  The random bits of element i are
+    tamd_sr_bits(sr_key(seed, ordinal), step, i) -- the same (seed, step, ordinal) gives the same bits, and
+    `TamdAdamW(stochastic_rounding=True, sr_seed=seed)` stores parameter `ordinal` at step `step` through exactly this."""
+    return T.sr_round_bf16(x, sr_key(seed, ordinal), int(step))
 
 
 def linear(x, w, bias=None, residual=None, act=ACT_NONE):

@@ -45,17 +45,23 @@ class MtTable:
         self.chunks = 0
         self._keep: tuple = ()
 
-    def update(self, ps, gs, ms, vs) -> "MtTable":
+    def update(self, ps, gs, ms, vs, keys=None) -> "MtTable":
+        """`keys`: one int64 word per tensor, appended as a seventh column after the plain table's words (the
+        stochastic-rounding keys of `tamd_mt_adamw_step_sr`); None: the plain 6n + 1 words."""
         n = len(gs)
         cols = [[t.data_ptr() for t in col] if col is not None else [0] * n for col in (ps, gs, ms, vs)]
         numel = [g.numel() for g in gs]
         key = (gs[0].device, tuple(cols[0]), tuple(cols[1]), tuple(cols[2]), tuple(cols[3]), tuple(numel))
+        if keys is not None:
+            key += (tuple(keys),)
         if key != self._key:
             start, c = [], 0
             for k in numel:
                 start.append(c)
                 c += -(-k // MT_CHUNK)
             words = cols[0] + cols[1] + cols[2] + cols[3] + numel + start + [c]
+            if keys is not None:
+                words += list(keys)
             self.table = torch.tensor(words, dtype=torch.int64).to(gs[0].device)
             self._key, self.n, self.chunks = key, n, c
         self._keep = (ps, gs, ms, vs)  # the table holds raw pointers: keep their owners alive until the next update
@@ -185,25 +191,50 @@ def install_trainer_clip() -> bool:
 
 
 class TamdAdamW(torch.optim.Optimizer):
+    """`stochastic_rounding=True`: bf16 parameters are stored by stochastic rounding (csrc/sround.h) instead of
+    round-to-nearest.  A bf16 weight of magnitude 0.02 has an ulp of 2^-13 = 1.2e-4; a step at lr = 2e-5 moves it by a sixth
+    of that, and round-to-nearest puts it back where it was -- on every step.  Rounded up or down with probability equal to
+    its position between the two bf16 neighbours, the expected stored value is the fp32 value and the small steps add up,
+    with no fp32 copy of the parameters.  fp32 parameters take the plain launch (nothing to round); fp16 parameters raise
+    ValueError at the first `step()` (fp16 training uses a GradScaler and fp32 master weights).
+
+    `sr_seed` (63 bits) selects the random bits: those of element i of parameter k (its position across all param_groups,
+    `state_dict()`'s numbering) at step t are a counter-based hash of (sr_seed, k, t, i) -- reproducible, independent of which
+    parameters have gradients, and restated by `ops.sr_round_bf16`.  `sr_seed=None` takes
+    `torch.initial_seed() & (2**63 - 1)` at construction: that reads the seed and draws nothing from the generator, so model
+    initialisation is undisturbed, and after `set_seed` it is the same on every DDP rank -- replicas round identically and
+    stay in sync.  Both are param-group entries: they are saved in `state_dict()["param_groups"]`, and a resumed run continues
+    with the same bits."""
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, *, fp32_moments=False,
-                 maximize=False, max_grad_norm: Optional[float] = None):
+                 maximize=False, max_grad_norm: Optional[float] = None, stochastic_rounding=False,
+                 sr_seed: Optional[int] = None):
         if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
             raise ValueError(f"invalid AdamW hyper-parameters: lr={lr} betas={betas} eps={eps} wd={weight_decay}")
         if max_grad_norm is not None and max_grad_norm < 0.0:
             raise ValueError(f"invalid max_grad_norm={max_grad_norm}")
+        if sr_seed is None:
+            sr_seed = torch.initial_seed()
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, fp32_moments=fp32_moments,
-                        maximize=maximize)
+                        maximize=maximize, stochastic_rounding=bool(stochastic_rounding),
+                        sr_seed=int(sr_seed) & (2 ** 63 - 1))
         super().__init__(params, defaults)
         self.max_grad_norm = max_grad_norm  # None / 0: no clipping.  One norm over ALL param groups, as Trainer's
         self.grad_norm: Optional[torch.Tensor] = None  # the pre-clip norm of the last step (device memory, 0-dim)
         self._tables: Dict[tuple, MtTable] = {}
         self._norm_state = _NormState()
+        self._sr_keys: Dict[Tuple[int, int], int] = {}  # (sr_seed, ordinal) -> key word: computed once per parameter
 
     def load_state_dict(self, state_dict):
         """torch.optim.Optimizer.load_state_dict casts every floating-point state tensor to its parameter's dtype: with
         `fp32_moments=True` and bf16 parameters a resumed run would silently continue on bf16 moments.  Re-install the
-        checkpoint's moments in the dtype this optimizer is configured for."""
+        checkpoint's moments in the dtype this optimizer is configured for.  The checkpoint's param_groups replace this
+        optimizer's: entries they lack (a checkpoint of torch.optim.AdamW, or one written before `stochastic_rounding`
+        existed) fall back to this optimizer's defaults."""
         super().load_state_dict(state_dict)
+        for group in self.param_groups:
+            for k, d in self.defaults.items():
+                group.setdefault(k, d)
         saved = state_dict["state"]
         ids = [i for g in state_dict["param_groups"] for i in g["params"]]
         params = [p for g in self.param_groups for p in g["params"]]
@@ -224,13 +255,19 @@ class TamdAdamW(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         # launches: every parameter of a (group, device, dtype, moment dtype, step count) in one table
-        launches: Dict[tuple, Tuple[list, list, list, list]] = {}
+        launches: Dict[tuple, Tuple[list, list, list, list, list]] = {}
         all_grads: List[torch.Tensor] = []
+        ordinal = -1  # position of a parameter across all groups (state_dict()'s numbering): what keys its rounding bits
         for gi, group in enumerate(self.param_groups):
             fresh, steps, entries = [], [], []
+            sr = bool(group["stochastic_rounding"])
             for p in group["params"]:
+                ordinal += 1
                 if p.grad is None:
                     continue
+                if sr and p.dtype == torch.float16:
+                    raise ValueError("TamdAdamW(stochastic_rounding=True) rounds bf16 parameters; fp16 training uses a "
+                                     "GradScaler and fp32 master weights")
                 if p.grad.is_sparse:
                     raise RuntimeError("TamdAdamW does not support sparse gradients")
                 if p.dtype not in _DTYPE_CODE:
@@ -246,7 +283,7 @@ class TamdAdamW(torch.optim.Optimizer):
                     fresh.append(st)
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 steps.append(st["step"])
-                entries.append((p, g, st))
+                entries.append((p, g, st, ordinal))
             if not entries:
                 continue
             cpu_steps = [s for s in steps if not s.is_cuda]
@@ -257,13 +294,14 @@ class TamdAdamW(torch.optim.Optimizer):
                 for s in steps:
                     s += 1
                 counts = [float(s) for s in steps]
-            for (p, g, st), t in zip(entries, counts):
+            for (p, g, st, k), t in zip(entries, counts):
                 key = (gi, p.device, p.dtype, st["exp_avg"].dtype, int(t))
-                cols = launches.setdefault(key, ([], [], [], []))
+                cols = launches.setdefault(key, ([], [], [], [], []))
                 cols[0].append(p)
                 cols[1].append(g)
                 cols[2].append(st["exp_avg"])
                 cols[3].append(st["exp_avg_sq"])
+                cols[4].append(k)
                 all_grads.append(g)
         if not launches:
             return loss
@@ -272,8 +310,10 @@ class TamdAdamW(torch.optim.Optimizer):
             out, _ = grad_norm(all_grads, self.max_grad_norm, self._norm_state)
             self.grad_norm = out[0]
             coef_by_dev[out.device] = out[1:2]
+        from .ops import sr_key  # (the one definition of the key on the Python side)
+
         live = set()
-        for key, (ps, gs, ms, vs) in launches.items():
+        for key, (ps, gs, ms, vs, ordinals) in launches.items():
             gi, dev, dt, mdt, t = key
             group = self.param_groups[gi]
             lr = group["lr"]
@@ -284,15 +324,26 @@ class TamdAdamW(torch.optim.Optimizer):
             if tkey in live:  # two step counts inside one group (parameters added later): a second table for the stragglers
                 tkey = key
             live.add(tkey)
-            tab = self._tables.setdefault(tkey, MtTable()).update(ps, gs, ms, vs)
+            # bf16 parameters of a stochastic-rounding group: the key column and the rounding launch; fp32 has nothing to round
+            sr = bool(group["stochastic_rounding"]) and dt == torch.bfloat16
+            keys = None
+            if sr:
+                seed = int(group["sr_seed"])
+                keys = [self._sr_keys.get((seed, k)) or self._sr_keys.setdefault((seed, k), sr_key(seed, k)) for k in ordinals]
+            tab = self._tables.setdefault(tkey, MtTable()).update(ps, gs, ms, vs, keys)
             coef = None
             if coef_by_dev:
                 coef = coef_by_dev.get(dev)
                 if coef is None:
                     coef = coef_by_dev[dev] = next(iter(coef_by_dev.values())).to(dev)
-            torch.ops.tamd.mt_adamw_step_(tab.table, tab.n, tab.chunks, float(lr), float(b1), float(b2),
-                                          float(group["eps"]), float(group["weight_decay"]), t,
-                                          -1.0 if group["maximize"] else 1.0, coef, _DTYPE_CODE[dt], _DTYPE_CODE[mdt])
+            if sr:
+                torch.ops.tamd.mt_adamw_step_sr_(tab.table, tab.n, tab.chunks, float(lr), float(b1), float(b2),
+                                                 float(group["eps"]), float(group["weight_decay"]), t,
+                                                 -1.0 if group["maximize"] else 1.0, coef, _DTYPE_CODE[mdt])
+            else:
+                torch.ops.tamd.mt_adamw_step_(tab.table, tab.n, tab.chunks, float(lr), float(b1), float(b2),
+                                              float(group["eps"]), float(group["weight_decay"]), t,
+                                              -1.0 if group["maximize"] else 1.0, coef, _DTYPE_CODE[dt], _DTYPE_CODE[mdt])
         for k in [k for k in self._tables if k not in live]:
             del self._tables[k]
         return loss
