@@ -222,25 +222,41 @@ def test_multi_tensor_step_equals_per_tensor_kernel(env, dtype, fp32_moments):
             assert opt.state[p]["exp_avg"].dtype == mdt
 
 
-def test_multi_tensor_step_without_clip_is_bit_identical(env):
-    """grad_scale 1: the table launch and the per-tensor kernel run the same arithmetic on the same bits."""
-    _, ps = _mixed_params(env.device, torch.bfloat16, False)
-    twins = [p.detach().clone() for p in ps]
-    twins[-1] = torch.cat([ps[-1].new_zeros(1), ps[-1].detach()])[1:]
-    opt = transformers_amd.TamdAdamW(ps, **HYP)
-    ms = [torch.zeros_like(p) for p in twins]
-    vs = [torch.zeros_like(p) for p in twins]
+@pytest.mark.parametrize("fp32_moments", [False, True])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+def test_multi_tensor_step_without_clip_is_bit_identical(env, dtype, fp32_moments):
+    """grad_scale 1: the table launch and the per-tensor kernel run the same arithmetic on the same bits, for both 16-bit
+    parameter types and both moment types.  A 0-dim tensor, a tail only, vector bodies with and without a tail, and a tensor
+    one element into its buffer (2 bytes past a 16-byte boundary: all of it takes the one-element loop)."""
+    shapes = [(), (3,), (37,), (5, 13), (256, 8), (2049,)]
+    torch.manual_seed(7)
+    host = [torch.randn(s).to(dtype) for s in shapes]
+
+    def on_device():  # the last tensor misaligned, in both sets
+        out = [t.clone().to(env.device) for t in host[:-1]]
+        return out + [torch.cat([host[-1].new_zeros(1), host[-1]]).to(env.device)[1:]]
+
+    ps = [torch.nn.Parameter(t) for t in on_device()]
+    twins = on_device()
+    assert ps[-1].data_ptr() % 16 == 2 and twins[-1].data_ptr() % 16 == 2 and ps[-1].is_contiguous()
+    opt = transformers_amd.TamdAdamW(ps, fp32_moments=fp32_moments, **HYP)
+    mdt = torch.float32 if fp32_moments else dtype
+    ms = [torch.zeros_like(q, dtype=mdt) for q in twins]
+    vs = [torch.zeros_like(q, dtype=mdt) for q in twins]
     torch.manual_seed(10)
     for t in range(2):
         for p, q, m, v in zip(ps, twins, ms, vs):
-            g = (torch.randn(p.shape) * 0.3).bfloat16().to(env.device)
+            g = (torch.randn(p.shape) * 0.3).to(dtype).to(env.device)
             p.grad = g.clone()
             ops.raw_adamw_step_(q.view(-1), g.view(-1), m.view(-1), v.view(-1), lr=HYP["lr"], beta1=HYP["betas"][0],
                                 beta2=HYP["betas"][1], eps=HYP["eps"], weight_decay=HYP["weight_decay"], step=t + 1)
         opt.step()
+    assert len(opt._tables) == 1
     for p, q, m, v in zip(ps, twins, ms, vs):
+        assert opt.state[p]["exp_avg"].dtype == mdt and opt.state[p]["exp_avg_sq"].dtype == mdt
         assert torch.equal(p.detach(), q)
         assert torch.equal(opt.state[p]["exp_avg"], m) and torch.equal(opt.state[p]["exp_avg_sq"], v)
+    assert not torch.equal(ps[-2].detach().cpu(), host[-2])  # (the steps did something)
 
 
 def test_param_groups_and_dtypes_launch_counts(env):

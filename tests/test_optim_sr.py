@@ -123,13 +123,18 @@ def test_sr_rounding_probability(env, low16):
         assert not np.array_equal(a, b)
 
 
-def _sr_twin_step(env, shapes, grads, seed, **kw):
+def _sr_twin_step(env, shapes, grads, seed, fp32_moments=True, misaligned=(), **kw):
     """One step of the stochastic-rounding optimizer on bf16 parameters, and one step of the plain optimizer on fp32 copies
-    with the same gradients upcast, its result rounded by ops.sr_round_bf16 with (seed, step 1, ordinal k)."""
+    with the same gradients upcast, its result rounded by ops.sr_round_bf16 with (seed, step 1, ordinal k).  With bf16
+    moments (first step only: they start at zero, so both runs evaluate the same fp32 expression) each moment is the fp32
+    twin's rounded to nearest.  `misaligned`: positions in `shapes` of parameters stored one element into their buffer."""
     g0 = torch.Generator().manual_seed(21)
-    ps = [torch.nn.Parameter(torch.randn(s, generator=g0).bfloat16().to(env.device)) for s in shapes]
+    host = [torch.randn(s, generator=g0).bfloat16() for s in shapes]
+    ps = [torch.nn.Parameter(torch.cat([t.new_zeros(1), t]).to(env.device)[1:] if k in misaligned else t.to(env.device))
+          for k, t in enumerate(host)]
+    assert all((p.data_ptr() % 16 == 2) == (k in misaligned) and p.is_contiguous() for k, p in enumerate(ps))
     p32 = [torch.nn.Parameter(p.detach().float().clone()) for p in ps]
-    opt = transformers_amd.TamdAdamW(ps, stochastic_rounding=True, fp32_moments=True, sr_seed=seed, **HYP, **kw)
+    opt = transformers_amd.TamdAdamW(ps, stochastic_rounding=True, fp32_moments=fp32_moments, sr_seed=seed, **HYP, **kw)
     ref = transformers_amd.TamdAdamW(p32, **HYP, **kw)
     for p, q, g in zip(ps, p32, grads):
         p.grad = g.bfloat16().to(env.device)
@@ -140,8 +145,9 @@ def _sr_twin_step(env, shapes, grads, seed, **kw):
         want = ops.sr_round_bf16(q.detach(), seed, step=1, ordinal=k)
         assert p.shape == q.shape and np.array_equal(_bits(p), _bits(want)), (k, tuple(p.shape))
         for name in ("exp_avg", "exp_avg_sq"):
-            assert opt.state[p][name].dtype == torch.float32
-            assert torch.equal(opt.state[p][name], ref.state[q][name]), (k, name)
+            got, twin = opt.state[p][name], ref.state[q][name]
+            assert got.dtype == (torch.float32 if fp32_moments else torch.bfloat16) and twin.dtype == torch.float32
+            assert torch.equal(got, twin.to(got.dtype)), (k, name)
     return opt, ref, ps, p32
 
 
@@ -158,6 +164,19 @@ def test_sr_optimizer_kernel_is_the_fp32_kernel_plus_rounding(env):
     assert tab.table[6 * len(shapes) + 1:].tolist() == [ops.sr_key(0x5EED, k) for k in range(len(shapes))]
     # and the rounding does something: a sizeable part of the big tensor differs from round-to-nearest, by one ulp
     rn, sr = _bits(p32[-1].detach().bfloat16()).astype(np.int32), _bits(ps[-1]).astype(np.int32)
+    assert 0.15 < (rn != sr).mean() < 0.35 and np.abs(rn - sr).max() == 1
+
+
+def test_sr_optimizer_kernel_with_bf16_moments_is_the_fp32_kernel_plus_rounding(env):
+    """3b: the same statement for bf16 moments -- eight elements per lane and a 16-byte parameter store, where test 3 (fp32
+    moments) has four and eight bytes.  The shapes of test 3 and a parameter whose storage is not 16-byte aligned (one
+    element per lane from start to end)."""
+    shapes = [(), (3,), (37,), (5, 13), (256, 64), (65537,), (2049,)]
+    g1 = torch.Generator().manual_seed(23)
+    grads = [torch.randn(s, generator=g1) * 0.3 for s in shapes]
+    opt, _, ps, p32 = _sr_twin_step(env, shapes, grads, seed=0xB16, fp32_moments=False, misaligned={len(shapes) - 1})
+    assert len(opt._tables) == 1
+    rn, sr = _bits(p32[-2].detach().bfloat16()).astype(np.int32), _bits(ps[-2]).astype(np.int32)
     assert 0.15 < (rn != sr).mean() < 0.35 and np.abs(rn - sr).max() == 1
 
 

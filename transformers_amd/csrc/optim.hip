@@ -13,6 +13,8 @@
 // HBM-bound: algorithmic bytes = (4 reads + 3 writes) x element size.
 #include <math.h>
 
+#include <type_traits>
+
 #include "common.h"
 #include "sround.h"
 
@@ -41,36 +43,6 @@ __device__ __forceinline__ void store_vec(T* ptr, const float* in) {
   }
 }
 
-template <typename T, typename S>
-__global__ void adamw_kernel(T* __restrict__ p, const T* __restrict__ g, S* __restrict__ m, S* __restrict__ v,
-                             int64_t n, float decay, float b1, float b2, float step_size, float inv_bc2_sqrt,
-                             float eps, float grad_scale) {
-  // VE elements per thread: one 16-byte access of the wider of the two storage types
-  constexpr int VE = vec16<T>::N < vec16<S>::N ? vec16<T>::N : vec16<S>::N;
-  for (int64_t idx = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * VE; idx < n;
-       idx += (int64_t)gridDim.x * blockDim.x * VE) {
-    float pp[VE], gg[VE], mm[VE], vv[VE];
-    load_vec<T, VE>(p + idx, pp);
-    load_vec<T, VE>(g + idx, gg);
-    load_vec<S, VE>(m + idx, mm);
-    load_vec<S, VE>(v + idx, vv);
-#pragma unroll
-    for (int i = 0; i < VE; ++i) {
-      const float gi = gg[i] * grad_scale;
-      const float pd = pp[i] * decay;
-      const float mn = mm[i] + (1.f - b1) * (gi - mm[i]);
-      const float vn = b2 * vv[i] + (1.f - b2) * gi * gi;
-      const float denom = sqrtf(vn) * inv_bc2_sqrt + eps;
-      pp[i] = pd - step_size * (mn / denom);
-      mm[i] = mn;
-      vv[i] = vn;
-    }
-    store_vec<T, VE>(p + idx, pp);
-    store_vec<S, VE>(m + idx, mm);
-    store_vec<S, VE>(v + idx, vv);
-  }
-}
-
 __device__ __forceinline__ float load1(const bf16_t* q) { return bf16_bits_to_f32(q->bits); }
 __device__ __forceinline__ float load1(const f16_t* q) { return f16_bits_to_f32(q->bits); }
 __device__ __forceinline__ float load1(const float* q) { return *q; }
@@ -78,43 +50,124 @@ __device__ __forceinline__ void store1(bf16_t* q, float f) { q->bits = f32_to_bf
 __device__ __forceinline__ void store1(f16_t* q, float f) { q->bits = f32_to_f16_bits(f); }
 __device__ __forceinline__ void store1(float* q, float f) { *q = f; }
 
-// elements [start, n) one per thread: the ragged tail (n % VE) of a tensor, or a whole tensor whose storage is not
-// 16-byte aligned (scalar parameters such as CLIP's logit_scale, a 2- or 3-label classifier bias)
+// what one step multiplies and adds with, the same for every element (adamw_coef); passed to the kernels by value
+struct AdamwCoef {
+  float decay, b1, b2, step_size, inv_bc2_sqrt, eps;
+};
+
+// The update of one element, for every kernel below: g is the gradient already scaled, m and v become the new moments, the new
+// parameter is returned.  (Built with -ffp-contract=off: these operations in this order wherever it is inlined.)
+__device__ __forceinline__ float adamw_update(const AdamwCoef& c, float g, float p, float& m, float& v) {
+  const float pd = p * c.decay;
+  m = m + (1.f - c.b1) * (g - m);
+  v = c.b2 * v + (1.f - c.b2) * g * g;
+  const float denom = sqrtf(v) * c.inv_bc2_sqrt + c.eps;
+  return pd - c.step_size * (m / denom);
+}
+
+// How the new parameter is stored (the moments move by more than an ulp per step and are always rounded to nearest): `i` is the
+// index inside its tensor of the (first) element stored.
+template <typename T>
+struct StoreNearest {
+  template <int VE>
+  __device__ __forceinline__ void vec(T* q, int64_t, const float* x) const {
+    store_vec<T, VE>(q, x);
+  }
+  __device__ __forceinline__ void one(T* q, int64_t, float x) const { store1(q, x); }
+};
+// Stochastic rounding of bf16 parameters (sround.h): the random bits of element i are sr_elem_bits(stream, i), stream =
+// sr_stream(key of the tensor, step) -- a function of the element, not of the chunk, the slot or the path (vector body /
+// one-element tail) that handles it.  A vector starts at a multiple of VE, so it covers whole element pairs: one hash (three
+// 32-bit multiplies) per pair.
+struct StoreStochastic {
+  unsigned long long stream;
+  template <int VE>
+  __device__ __forceinline__ void vec(bf16_t* q, int64_t i, const float* x) const {
+    const unsigned long long pair0 = (unsigned long long)i >> 1;
+    unsigned int pw[VE / 2];
+#pragma unroll
+    for (int e = 0; e < VE / 2; ++e) pw[e] = sr_pack2_bf16(x[2 * e], x[2 * e + 1], sr_pair_word(stream, pair0 + e));
+    if constexpr (VE == 8) {
+      st16(q, u32x4{pw[0], pw[1], pw[2], pw[3]});
+    } else {
+      st8(q, u32x2{pw[0], pw[1]});
+    }
+  }
+  __device__ __forceinline__ void one(bf16_t* q, int64_t i, float x) const {
+    q->bits = sr_bf16(x, sr_elem_bits(stream, (unsigned long long)i));
+  }
+};
+
+// VE elements per thread and trip: one 16-byte access of the wider of the two storage types
 template <typename T, typename S>
-__global__ void adamw_scalar_kernel(T* __restrict__ p, const T* __restrict__ g, S* __restrict__ m, S* __restrict__ v,
-                                    int64_t start, int64_t n, float decay, float b1, float b2, float step_size,
-                                    float inv_bc2_sqrt, float eps, float grad_scale) {
-  for (int64_t idx = start + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n;
-       idx += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = load1(g + idx) * grad_scale;
-    const float pd = load1(p + idx) * decay;
-    const float m0 = load1(m + idx), v0 = load1(v + idx);
-    const float mn = m0 + (1.f - b1) * (gi - m0);
-    const float vn = b2 * v0 + (1.f - b2) * gi * gi;
-    const float denom = sqrtf(vn) * inv_bc2_sqrt + eps;
-    store1(p + idx, pd - step_size * (mn / denom));
-    store1(m + idx, mn);
-    store1(v + idx, vn);
+constexpr int adamw_ve() {
+  return vec16<T>::N < vec16<S>::N ? vec16<T>::N : vec16<S>::N;
+}
+
+// The two loops of every AdamW kernel, run by thread `tid` of `nthreads` (a whole grid, or the one workgroup of a chunk) over a
+// span of a tensor that begins at the tensor's element `first`.  Elements [0, n_vec) of the span, 16-byte aligned and n_vec a
+// multiple of VE, streamed VE per thread:
+template <typename T, typename S, typename Store>
+__device__ __forceinline__ void adamw_vec_span(T* p, const T* g, S* m, S* v, int64_t n_vec, int64_t first, int64_t tid,
+                                               int64_t nthreads, const AdamwCoef& c, float grad_scale, const Store& store) {
+  constexpr int VE = adamw_ve<T, S>();
+  for (int64_t idx = tid * VE; idx < n_vec; idx += nthreads * VE) {
+    float pp[VE], gg[VE], mm[VE], vv[VE];
+    load_vec<T, VE>(p + idx, pp);
+    load_vec<T, VE>(g + idx, gg);
+    load_vec<S, VE>(m + idx, mm);
+    load_vec<S, VE>(v + idx, vv);
+#pragma unroll
+    for (int i = 0; i < VE; ++i) pp[i] = adamw_update(c, gg[i] * grad_scale, pp[i], mm[i], vv[i]);
+    store.template vec<VE>(p + idx, first + idx, pp);
+    store_vec<S, VE>(m + idx, mm);
+    store_vec<S, VE>(v + idx, vv);
+  }
+}
+// ... and elements [start, n) one per thread: the ragged tail (n % VE), or all of a span whose storage is not 16-byte aligned
+// (scalar parameters such as CLIP's logit_scale, a 2- or 3-label classifier bias)
+template <typename T, typename S, typename Store>
+__device__ __forceinline__ void adamw_tail_span(T* p, const T* g, S* m, S* v, int64_t start, int64_t n, int64_t first,
+                                                int64_t tid, int64_t nthreads, const AdamwCoef& c, float grad_scale,
+                                                const Store& store) {
+  for (int64_t idx = start + tid; idx < n; idx += nthreads) {
+    float m1 = load1(m + idx), v1 = load1(v + idx);
+    store.one(p + idx, first + idx, adamw_update(c, load1(g + idx) * grad_scale, load1(p + idx), m1, v1));
+    store1(m + idx, m1);
+    store1(v + idx, v1);
   }
 }
 
 template <typename T, typename S>
-static int adamw_launch(void* p, const void* g, void* m, void* v, int64_t n, float decay, float b1, float b2,
-                        float step_size, float inv_bc2_sqrt, float eps, float grad_scale, hipStream_t s) {
-  constexpr int VE = vec16<T>::N < vec16<S>::N ? vec16<T>::N : vec16<S>::N;
+__global__ void adamw_kernel(T* __restrict__ p, const T* __restrict__ g, S* __restrict__ m, S* __restrict__ v,
+                             int64_t n, AdamwCoef c, float grad_scale) {
+  adamw_vec_span(p, g, m, v, n, 0, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x, c,
+                 grad_scale, StoreNearest<T>{});
+}
+template <typename T, typename S>
+__global__ void adamw_scalar_kernel(T* __restrict__ p, const T* __restrict__ g, S* __restrict__ m, S* __restrict__ v,
+                                    int64_t start, int64_t n, AdamwCoef c, float grad_scale) {
+  adamw_tail_span(p, g, m, v, start, n, 0, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x, c,
+                  grad_scale, StoreNearest<T>{});
+}
+
+template <typename T, typename S>
+static int adamw_launch(void* p, const void* g, void* m, void* v, int64_t n, const AdamwCoef& c, float grad_scale,
+                        hipStream_t s) {
+  constexpr int VE = adamw_ve<T, S>();
   const bool vec_ok = aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v);
   const int64_t n_vec = vec_ok ? n - n % VE : 0;  // streamed 16 bytes per lane; the rest one element per thread
   if (n_vec > 0) {
     int64_t blocks = ceil_div(n_vec / VE, 256);
     if (blocks > 256 * 16) blocks = 256 * 16;  // grid-stride beyond 16 workgroups per CU
     hipLaunchKernelGGL((adamw_kernel<T, S>), dim3((unsigned)blocks), dim3(256), 0, s, (T*)p, (const T*)g, (S*)m, (S*)v,
-                       n_vec, decay, b1, b2, step_size, inv_bc2_sqrt, eps, grad_scale);
+                       n_vec, c, grad_scale);
   }
   if (n_vec < n) {
     int64_t blocks = ceil_div(n - n_vec, 256);
     if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL((adamw_scalar_kernel<T, S>), dim3((unsigned)blocks), dim3(256), 0, s, (T*)p, (const T*)g, (S*)m,
-                       (S*)v, n_vec, n, decay, b1, b2, step_size, inv_bc2_sqrt, eps, grad_scale);
+                       (S*)v, n_vec, n, c, grad_scale);
   }
   return launch_status();
 }
@@ -131,7 +184,8 @@ static int adamw_launch(void* p, const void* g, void* m, void* v, int64_t n, flo
 //     mt_norm_finish     one workgroup: norm = sqrt(sum of partials), coef = min(1, max_norm / (norm + 1e-6)) -- the
 //                        reference's clamp -- left in device memory (out[0], out[1]); nobody reads it back on the host
 //     mt_adamw_kernel    one launch for every tensor of the table; the gradient is scaled by grad_scale * *grad_scale_dev
-//                        in registers (the clipped gradient never goes back to HBM)
+//                        in registers (the clipped gradient never goes back to HBM).  <T, S, SR = true>: bf16 parameters
+//                        stored by stochastic rounding, keyed by one more column, words [6n+1, 7n+1)
 // (mt_scale_kernel scales the gradients in place, for callers that want torch.nn.utils.clip_grad_norm_'s side effect.)
 // Table (int64 words, device memory), n tensors:  [0,n) p | [n,2n) g | [2n,3n) m | [3n,4n) v | [4n,5n) numel |
 // [5n,6n] first chunk of tensor i (prefix sum of ceil(numel / kMtChunk)); word 6n = total chunks.
@@ -250,11 +304,12 @@ __global__ __launch_bounds__(kMtThreads) void mt_scale_kernel(const int64_t* __r
   for (int64_t i = n_vec + threadIdx.x; i < s.count; i += kMtThreads) store1(g + i, load1(g + i) * coef);
 }
 
-template <typename T, typename S>
-__global__ __launch_bounds__(kMtThreads) void mt_adamw_kernel(const int64_t* __restrict__ table, int n, float decay, float b1,
-                                                              float b2, float step_size, float inv_bc2_sqrt, float eps,
-                                                              float grad_scale, const float* __restrict__ grad_scale_dev) {
-  constexpr int VE = vec16<T>::N < vec16<S>::N ? vec16<T>::N : vec16<S>::N;
+// SR: the parameter (bf16) is stored through StoreStochastic; only this form reads the key column, words [6n+1, 7n+1)
+template <typename T, typename S, bool SR>
+__global__ __launch_bounds__(kMtThreads) void mt_adamw_kernel(const int64_t* __restrict__ table, int n, AdamwCoef c,
+                                                              float grad_scale, const float* __restrict__ grad_scale_dev,
+                                                              unsigned long long step) {
+  constexpr int VE = adamw_ve<T, S>();
   const MtSlot s = mt_slot(table, n, blockIdx.x);
   if (s.count <= 0) return;
   const int64_t nn = n;
@@ -265,107 +320,16 @@ __global__ __launch_bounds__(kMtThreads) void mt_adamw_kernel(const int64_t* __r
   const float gs = grad_scale_dev != nullptr ? grad_scale * *grad_scale_dev : grad_scale;
   const uintptr_t mis = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
                         reinterpret_cast<uintptr_t>(v);
+  // (chunks start at multiples of 64 Ki elements: s.first + a multiple of VE is a multiple of VE)
   const int64_t n_vec = (mis & 15u) == 0 ? s.count - s.count % VE : 0;
-  for (int64_t idx = (int64_t)threadIdx.x * VE; idx < n_vec; idx += (int64_t)kMtThreads * VE) {
-    float pp[VE], gg[VE], mm[VE], vv[VE];
-    load_vec<T, VE>(p + idx, pp);
-    load_vec<T, VE>(g + idx, gg);
-    load_vec<S, VE>(m + idx, mm);
-    load_vec<S, VE>(v + idx, vv);
-#pragma unroll
-    for (int i = 0; i < VE; ++i) {  // (the arithmetic of adamw_kernel, operation for operation)
-      const float gi = gg[i] * gs;
-      const float pd = pp[i] * decay;
-      const float mn = mm[i] + (1.f - b1) * (gi - mm[i]);
-      const float vn = b2 * vv[i] + (1.f - b2) * gi * gi;
-      const float denom = sqrtf(vn) * inv_bc2_sqrt + eps;
-      pp[i] = pd - step_size * (mn / denom);
-      mm[i] = mn;
-      vv[i] = vn;
-    }
-    store_vec<T, VE>(p + idx, pp);
-    store_vec<S, VE>(m + idx, mm);
-    store_vec<S, VE>(v + idx, vv);
-  }
-  for (int64_t idx = n_vec + threadIdx.x; idx < s.count; idx += kMtThreads) {
-    const float gi = load1(g + idx) * gs;
-    const float pd = load1(p + idx) * decay;
-    const float m0 = load1(m + idx), v0 = load1(v + idx);
-    const float mn = m0 + (1.f - b1) * (gi - m0);
-    const float vn = b2 * v0 + (1.f - b2) * gi * gi;
-    const float denom = sqrtf(vn) * inv_bc2_sqrt + eps;
-    store1(p + idx, pd - step_size * (mn / denom));
-    store1(m + idx, mn);
-    store1(v + idx, vn);
-  }
-}
-
-// ---- stochastic rounding of bf16 parameters (sround.h).  mt_adamw_kernel<bf16_t, S> with the parameter stored through sr_bf16:
-// the random bits of element i of tensor t at step `step` are sr_bits(key[t], step, i), key = table words [6n+1, 7n+1) -- a
-// function of the element, not of the chunk, the slot or the path (vector body / one-element tail) that handles it.  Chunks
-// start at multiples of 64 Ki elements and a vector at a multiple of VE, so a vector covers whole element pairs: one hash
-// (three 32-bit multiplies) per pair.  The moments move by more than an ulp per step and are stored round-to-nearest.
-template <typename S>
-__global__ __launch_bounds__(kMtThreads) void mt_adamw_sr_kernel(const int64_t* __restrict__ table, int n, float decay, float b1,
-                                                                 float b2, float step_size, float inv_bc2_sqrt, float eps,
-                                                                 float grad_scale, const float* __restrict__ grad_scale_dev,
-                                                                 unsigned long long step) {
-  typedef bf16_t T;
-  constexpr int VE = vec16<T>::N < vec16<S>::N ? vec16<T>::N : vec16<S>::N;
-  const MtSlot s = mt_slot(table, n, blockIdx.x);
-  if (s.count <= 0) return;
-  const int64_t nn = n;
-  T* p = reinterpret_cast<T*>(table[s.tensor]) + s.first;
-  const T* g = reinterpret_cast<const T*>(table[nn + s.tensor]) + s.first;
-  S* m = reinterpret_cast<S*>(table[2 * nn + s.tensor]) + s.first;
-  S* v = reinterpret_cast<S*>(table[3 * nn + s.tensor]) + s.first;
-  const unsigned long long stream = sr_stream((unsigned long long)table[6 * nn + 1 + s.tensor], step);
-  const float gs = grad_scale_dev != nullptr ? grad_scale * *grad_scale_dev : grad_scale;
-  const uintptr_t mis = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                        reinterpret_cast<uintptr_t>(v);
-  const int64_t n_vec = (mis & 15u) == 0 ? s.count - s.count % VE : 0;
-  for (int64_t idx = (int64_t)threadIdx.x * VE; idx < n_vec; idx += (int64_t)kMtThreads * VE) {
-    float pp[VE], gg[VE], mm[VE], vv[VE];
-    load_vec<T, VE>(p + idx, pp);
-    load_vec<T, VE>(g + idx, gg);
-    load_vec<S, VE>(m + idx, mm);
-    load_vec<S, VE>(v + idx, vv);
-#pragma unroll
-    for (int i = 0; i < VE; ++i) {  // (the arithmetic of adamw_kernel, operation for operation)
-      const float gi = gg[i] * gs;
-      const float pd = pp[i] * decay;
-      const float mn = mm[i] + (1.f - b1) * (gi - mm[i]);
-      const float vn = b2 * vv[i] + (1.f - b2) * gi * gi;
-      const float denom = sqrtf(vn) * inv_bc2_sqrt + eps;
-      pp[i] = pd - step_size * (mn / denom);
-      mm[i] = mn;
-      vv[i] = vn;
-    }
-    const unsigned long long pair0 = (unsigned long long)(s.first + idx) >> 1;  // s.first + idx is a multiple of VE
-    unsigned int pw[VE / 2];
-#pragma unroll
-    for (int i = 0; i < VE / 2; ++i) pw[i] = sr_pack2_bf16(pp[2 * i], pp[2 * i + 1], sr_pair_word(stream, pair0 + i));
-    if constexpr (VE == 8) {
-      st16(p + idx, u32x4{pw[0], pw[1], pw[2], pw[3]});
-    } else {
-      st8(p + idx, u32x2{pw[0], pw[1]});
-    }
-    store_vec<S, VE>(m + idx, mm);
-    store_vec<S, VE>(v + idx, vv);
-  }
-  for (int64_t idx = n_vec + threadIdx.x; idx < s.count; idx += kMtThreads) {
-    const float gi = load1(g + idx) * gs;
-    const float pd = load1(p + idx) * decay;
-    const float m0 = load1(m + idx), v0 = load1(v + idx);
-    const float mn = m0 + (1.f - b1) * (gi - m0);
-    const float vn = b2 * v0 + (1.f - b2) * gi * gi;
-    const float denom = sqrtf(vn) * inv_bc2_sqrt + eps;
-    const unsigned long long i = (unsigned long long)(s.first + idx);
-    const unsigned w = sr_pair_word(stream, i >> 1);
-    p[idx].bits = sr_bf16(pd - step_size * (mn / denom), (i & 1) ? (w >> 16) : (w & 0xffffu));
-    store1(m + idx, mn);
-    store1(v + idx, vn);
-  }
+  const auto chunk = [&](const auto& store) {
+    adamw_vec_span(p, g, m, v, n_vec, s.first, threadIdx.x, kMtThreads, c, gs, store);
+    adamw_tail_span(p, g, m, v, n_vec, s.count, s.first, threadIdx.x, kMtThreads, c, gs, store);
+  };
+  if constexpr (SR)
+    chunk(StoreStochastic{sr_stream((unsigned long long)table[6 * nn + 1 + s.tensor], step)});
+  else
+    chunk(StoreNearest<T>{});
 }
 
 // y[i] = sr_bf16(x[i], sr_bits(key, step, i)): eight elements per lane (two 16-byte loads, one 16-byte store) while both
@@ -384,36 +348,45 @@ __global__ __launch_bounds__(256) void sr_round_kernel(const float* __restrict__
     for (int i = 0; i < 4; ++i) out[i] = sr_pack2_bf16(xx[2 * i], xx[2 * i + 1], sr_pair_word(stream, pair0 + i));
     st16(y + idx, out);
   }
-  for (int64_t idx = n_vec + tid; idx < n; idx += stride) {
-    const unsigned w = sr_pair_word(stream, (unsigned long long)idx >> 1);
-    y[idx].bits = sr_bf16(x[idx], (idx & 1) ? (w >> 16) : (w & 0xffffu));
-  }
+  for (int64_t idx = n_vec + tid; idx < n; idx += stride) y[idx].bits = sr_bf16(x[idx], sr_elem_bits(stream, idx));
 }
 
 }  // namespace tamd
 
 using namespace tamd;
 
+// step / beta validation and the bias corrections, in double on the host as torch does (torch/optim/adam.py: python floats)
+static int adamw_coef(double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step, AdamwCoef* c) {
+  if (step < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return TAMD_E_ARG;
+  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  c->decay = (float)(1.0 - lr * weight_decay);
+  c->b1 = (float)beta1;
+  c->b2 = (float)beta2;
+  c->step_size = (float)(lr / bc1);
+  c->inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+  c->eps = (float)eps;
+  return TAMD_OK;
+}
+
+// The five (parameter, moment) storage pairs of the AdamW kernels -- the moments in fp32 or in the parameter's own type -- as
+// `T` and `S` inside the statement.  Another parameter dtype returns TAMD_E_DTYPE; another moment dtype falls through.
+#define TAMD_DISPATCH_ADAMW_PAIR(dtype, state_dtype, ...)    \
+  if ((state_dtype) == TAMD_F32) {                            \
+    typedef float S;                                          \
+    TAMD_DISPATCH_DTYPE(dtype, __VA_ARGS__)                   \
+  } else if ((state_dtype) == (dtype)) {                      \
+    TAMD_DISPATCH_DTYPE(dtype, typedef T S; __VA_ARGS__)      \
+  }
+
 extern "C" int tamd_adamw_step(void* p, const void* g, void* m, void* v, int64_t n, double lr, double beta1,
                                double beta2, double eps, double weight_decay, int64_t step, double grad_scale,
                                int dtype, int state_dtype, tamd_stream_t stream) {
   if (!p || !g || !m || !v) return TAMD_E_NULL;
   if (n <= 0) return TAMD_OK;
-  if (step < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return TAMD_E_ARG;
-  // bias corrections in double on the host, as torch does (torch/optim/adam.py: python floats)
-  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-  const float step_size = (float)(lr / bc1), inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-  const float decay = (float)(1.0 - lr * weight_decay);
-  hipStream_t s = TAMD_STREAM(stream);
-#define TAMD_ADAMW(T_, S_)                                                                                        \
-  return adamw_launch<T_, S_>(p, g, m, v, n, decay, (float)beta1, (float)beta2, step_size, inv_bc2_sqrt, (float)eps, \
-                              (float)grad_scale, s)
-  if (dtype == TAMD_BF16 && state_dtype == TAMD_BF16) TAMD_ADAMW(bf16_t, bf16_t);
-  if (dtype == TAMD_BF16 && state_dtype == TAMD_F32) TAMD_ADAMW(bf16_t, float);
-  if (dtype == TAMD_F16 && state_dtype == TAMD_F16) TAMD_ADAMW(f16_t, f16_t);
-  if (dtype == TAMD_F16 && state_dtype == TAMD_F32) TAMD_ADAMW(f16_t, float);
-  if (dtype == TAMD_F32 && state_dtype == TAMD_F32) TAMD_ADAMW(float, float);
-#undef TAMD_ADAMW
+  AdamwCoef c;
+  if (const int err = adamw_coef(lr, beta1, beta2, eps, weight_decay, step, &c)) return err;
+  TAMD_DISPATCH_ADAMW_PAIR(dtype, state_dtype,
+                           return adamw_launch<T, S>(p, g, m, v, n, c, (float)grad_scale, TAMD_STREAM(stream)));
   return TAMD_E_DTYPE;
 }
 
@@ -447,31 +420,36 @@ extern "C" int tamd_mt_scale(const int64_t* table, int n_tensors, int64_t total_
   return launch_status();
 }
 
-extern "C" int tamd_mt_adamw_step(const int64_t* table, int n_tensors, int64_t total_chunks, double lr, double beta1,
-                                  double beta2, double eps, double weight_decay, int64_t step, double grad_scale,
-                                  const float* grad_scale_dev, int dtype, int state_dtype, tamd_stream_t stream) {
+// one launch for every tensor of the table.  SR: only bf16 parameters have the stochastic store (any other pair is a dtype error)
+template <bool SR>
+static int mt_adamw_step(const int64_t* table, int n_tensors, int64_t total_chunks, double lr, double beta1, double beta2,
+                         double eps, double weight_decay, int64_t step, double grad_scale, const float* grad_scale_dev,
+                         int dtype, int state_dtype, tamd_stream_t stream) {
   if (n_tensors <= 0 || total_chunks <= 0) return TAMD_OK;
   if (!table) return TAMD_E_NULL;
   if (total_chunks > 0x7fffffffLL) return TAMD_E_ARG;
-  if (step < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return TAMD_E_ARG;
-  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-  const float step_size = (float)(lr / bc1), inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-  const float decay = (float)(1.0 - lr * weight_decay);
-  hipStream_t s = TAMD_STREAM(stream);
-#define TAMD_MT_ADAMW(T_, S_)                                                                                            \
-  {                                                                                                                      \
-    hipLaunchKernelGGL((mt_adamw_kernel<T_, S_>), dim3((unsigned)total_chunks), dim3(kMtThreads), 0, s, table, n_tensors, \
-                       decay, (float)beta1, (float)beta2, step_size, inv_bc2_sqrt, (float)eps, (float)grad_scale,        \
-                       grad_scale_dev);                                                                                  \
-    return launch_status();                                                                                              \
-  }
-  if (dtype == TAMD_BF16 && state_dtype == TAMD_BF16) TAMD_MT_ADAMW(bf16_t, bf16_t);
-  if (dtype == TAMD_BF16 && state_dtype == TAMD_F32) TAMD_MT_ADAMW(bf16_t, float);
-  if (dtype == TAMD_F16 && state_dtype == TAMD_F16) TAMD_MT_ADAMW(f16_t, f16_t);
-  if (dtype == TAMD_F16 && state_dtype == TAMD_F32) TAMD_MT_ADAMW(f16_t, float);
-  if (dtype == TAMD_F32 && state_dtype == TAMD_F32) TAMD_MT_ADAMW(float, float);
-#undef TAMD_MT_ADAMW
+  AdamwCoef c;
+  if (const int err = adamw_coef(lr, beta1, beta2, eps, weight_decay, step, &c)) return err;
+  TAMD_DISPATCH_ADAMW_PAIR(dtype, state_dtype, if constexpr (!SR || std::is_same<T, bf16_t>::value) {
+    hipLaunchKernelGGL((mt_adamw_kernel<T, S, SR>), dim3((unsigned)total_chunks), dim3(kMtThreads), 0, TAMD_STREAM(stream),
+                       table, n_tensors, c, (float)grad_scale, grad_scale_dev, (unsigned long long)step);
+    return launch_status();
+  });
   return TAMD_E_DTYPE;
+}
+
+extern "C" int tamd_mt_adamw_step(const int64_t* table, int n_tensors, int64_t total_chunks, double lr, double beta1,
+                                  double beta2, double eps, double weight_decay, int64_t step, double grad_scale,
+                                  const float* grad_scale_dev, int dtype, int state_dtype, tamd_stream_t stream) {
+  return mt_adamw_step<false>(table, n_tensors, total_chunks, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
+                              grad_scale_dev, dtype, state_dtype, stream);
+}
+
+extern "C" int tamd_mt_adamw_step_sr(const int64_t* table, int n_tensors, int64_t total_chunks, double lr, double beta1,
+                                     double beta2, double eps, double weight_decay, int64_t step, double grad_scale,
+                                     const float* grad_scale_dev, int state_dtype, tamd_stream_t stream) {
+  return mt_adamw_step<true>(table, n_tensors, total_chunks, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
+                             grad_scale_dev, TAMD_BF16, state_dtype, stream);
 }
 
 extern "C" uint32_t tamd_sr_bits(uint64_t key, uint64_t step, uint64_t index) { return sr_bits(key, step, index); }
@@ -485,29 +463,5 @@ extern "C" int tamd_sr_round(const float* x, void* y_bf16, int64_t n, uint64_t k
   if (blocks > 256 * 16) blocks = 256 * 16;  // grid-stride beyond 16 workgroups per CU
   hipLaunchKernelGGL(sr_round_kernel, dim3((unsigned)blocks), dim3(256), 0, TAMD_STREAM(stream), x, (bf16_t*)y_bf16, n_vec, n,
                      (unsigned long long)key, (unsigned long long)step);
-  return launch_status();
-}
-
-extern "C" int tamd_mt_adamw_step_sr(const int64_t* table, int n_tensors, int64_t total_chunks, double lr, double beta1,
-                                     double beta2, double eps, double weight_decay, int64_t step, double grad_scale,
-                                     const float* grad_scale_dev, int state_dtype, tamd_stream_t stream) {
-  if (n_tensors <= 0 || total_chunks <= 0) return TAMD_OK;
-  if (!table) return TAMD_E_NULL;
-  if (total_chunks > 0x7fffffffLL) return TAMD_E_ARG;
-  if (step < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return TAMD_E_ARG;
-  if (state_dtype != TAMD_BF16 && state_dtype != TAMD_F32) return TAMD_E_DTYPE;
-  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-  const float step_size = (float)(lr / bc1), inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-  const float decay = (float)(1.0 - lr * weight_decay);
-  hipStream_t s = TAMD_STREAM(stream);
-#define TAMD_MT_ADAMW_SR(S_)                                                                                            \
-  hipLaunchKernelGGL((mt_adamw_sr_kernel<S_>), dim3((unsigned)total_chunks), dim3(kMtThreads), 0, s, table, n_tensors, \
-                     decay, (float)beta1, (float)beta2, step_size, inv_bc2_sqrt, (float)eps, (float)grad_scale,        \
-                     grad_scale_dev, (unsigned long long)step)
-  if (state_dtype == TAMD_BF16)
-    TAMD_MT_ADAMW_SR(bf16_t);
-  else
-    TAMD_MT_ADAMW_SR(float);
-#undef TAMD_MT_ADAMW_SR
   return launch_status();
 }

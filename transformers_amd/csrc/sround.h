@@ -41,9 +41,13 @@ __host__ __device__ __forceinline__ unsigned long long sr_stream(unsigned long l
 __host__ __device__ __forceinline__ unsigned sr_pair_word(unsigned long long stream, unsigned long long pair) {
   return dropout_hash((unsigned)stream, (unsigned)(stream >> 32), (unsigned)pair, (unsigned)(pair >> 32));
 }
-__host__ __device__ __forceinline__ unsigned sr_bits(unsigned long long key, unsigned long long step, unsigned long long i) {
-  const unsigned w = sr_pair_word(sr_stream(key, step), i >> 1);
+// r16 of element i of the stream's tensor
+__host__ __device__ __forceinline__ unsigned sr_elem_bits(unsigned long long stream, unsigned long long i) {
+  const unsigned w = sr_pair_word(stream, i >> 1);
   return (i & 1) ? (w >> 16) : (w & 0xffffu);
+}
+__host__ __device__ __forceinline__ unsigned sr_bits(unsigned long long key, unsigned long long step, unsigned long long i) {
+  return sr_elem_bits(sr_stream(key, step), i);
 }
 
 __host__ __device__ __forceinline__ unsigned short sr_bf16(float x, unsigned r16) {

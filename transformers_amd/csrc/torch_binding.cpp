@@ -462,18 +462,34 @@ void k_mt_scale_(const Tensor& table, int64_t n_tensors, int64_t total_chunks, c
                             L.stream),
         "tamd_mt_scale");
 }
+// the checks and the launch of both AdamW table ops.  `sr`: tamd_mt_adamw_step_sr, which reads the key column after the plain
+// table's words and takes no parameter dtype (bf16)
+void mt_adamw_launch(const char* op, bool sr, const Tensor& table, int64_t n_tensors, int64_t total_chunks, double lr, double beta1,
+                     double beta2, double eps, double weight_decay, int64_t step, double grad_scale,
+                     const OptTensor& grad_scale_dev, int64_t dtype, int64_t state_dtype) {
+  check_mt_table(table, n_tensors, total_chunks);
+  TORCH_CHECK(!sr || table.numel() >= 7 * n_tensors + 1, "tamd: ", op,
+              " needs the table with the key column (7 * n_tensors + 1 words)");
+  if (grad_scale_dev.has_value() && grad_scale_dev->defined())
+    TORCH_CHECK(grad_scale_dev->scalar_type() == at::kFloat && grad_scale_dev->numel() >= 1, "tamd: ", op,
+                " grad_scale_dev must be an fp32 scalar in device memory");
+  Launch L({&table, p(grad_scale_dev)});
+  const int64_t* words = (const int64_t*)ptr(table);
+  const float* scale_dev = (const float*)ptr(grad_scale_dev);
+  if (sr)
+    check(api().tamd_mt_adamw_step_sr(words, (int)n_tensors, total_chunks, lr, beta1, beta2, eps, weight_decay, step,
+                                      grad_scale, scale_dev, (int)state_dtype, L.stream),
+          "tamd_mt_adamw_step_sr");
+  else
+    check(api().tamd_mt_adamw_step(words, (int)n_tensors, total_chunks, lr, beta1, beta2, eps, weight_decay, step,
+                                   grad_scale, scale_dev, (int)dtype, (int)state_dtype, L.stream),
+          "tamd_mt_adamw_step");
+}
 void k_mt_adamw_step_(const Tensor& table, int64_t n_tensors, int64_t total_chunks, double lr, double beta1, double beta2,
                       double eps, double weight_decay, int64_t step, double grad_scale, const OptTensor& grad_scale_dev,
                       int64_t dtype, int64_t state_dtype) {
-  check_mt_table(table, n_tensors, total_chunks);
-  if (grad_scale_dev.has_value() && grad_scale_dev->defined())
-    TORCH_CHECK(grad_scale_dev->scalar_type() == at::kFloat && grad_scale_dev->numel() >= 1,
-                "tamd: mt_adamw_step_ grad_scale_dev must be an fp32 scalar in device memory");
-  Launch L({&table, p(grad_scale_dev)});
-  check(api().tamd_mt_adamw_step((const int64_t*)ptr(table), (int)n_tensors, total_chunks, lr, beta1, beta2, eps,
-                                 weight_decay, step, grad_scale, (const float*)ptr(grad_scale_dev), (int)dtype,
-                                 (int)state_dtype, L.stream),
-        "tamd_mt_adamw_step");
+  mt_adamw_launch("mt_adamw_step_", false, table, n_tensors, total_chunks, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
+                  grad_scale_dev, dtype, state_dtype);
 }
 // ---- stochastic rounding (include/tamd.h "stochastic rounding of bf16 parameters"): `key` is the tensor's 64-bit word as
 // the int64 of the same bits
@@ -489,17 +505,8 @@ Tensor k_sr_round_bf16(const Tensor& x_, int64_t key, int64_t step) {
 void k_mt_adamw_step_sr_(const Tensor& table, int64_t n_tensors, int64_t total_chunks, double lr, double beta1, double beta2,
                          double eps, double weight_decay, int64_t step, double grad_scale, const OptTensor& grad_scale_dev,
                          int64_t state_dtype) {
-  check_mt_table(table, n_tensors, total_chunks);
-  TORCH_CHECK(table.numel() >= 7 * n_tensors + 1,
-              "tamd: mt_adamw_step_sr_ needs the table with the key column (7 * n_tensors + 1 words)");
-  if (grad_scale_dev.has_value() && grad_scale_dev->defined())
-    TORCH_CHECK(grad_scale_dev->scalar_type() == at::kFloat && grad_scale_dev->numel() >= 1,
-                "tamd: mt_adamw_step_sr_ grad_scale_dev must be an fp32 scalar in device memory");
-  Launch L({&table, p(grad_scale_dev)});
-  check(api().tamd_mt_adamw_step_sr((const int64_t*)ptr(table), (int)n_tensors, total_chunks, lr, beta1, beta2, eps,
-                                    weight_decay, step, grad_scale, (const float*)ptr(grad_scale_dev), (int)state_dtype,
-                                    L.stream),
-        "tamd_mt_adamw_step_sr");
+  mt_adamw_launch("mt_adamw_step_sr_", true, table, n_tensors, total_chunks, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
+                  grad_scale_dev, TAMD_BF16, state_dtype);
 }
 
 Tensor k_colsum(const Tensor& x2d) {

@@ -336,14 +336,12 @@ class TamdAdamW(torch.optim.Optimizer):
                 coef = coef_by_dev.get(dev)
                 if coef is None:
                     coef = coef_by_dev[dev] = next(iter(coef_by_dev.values())).to(dev)
+            args = (tab.table, tab.n, tab.chunks, float(lr), float(b1), float(b2), float(group["eps"]),
+                    float(group["weight_decay"]), t, -1.0 if group["maximize"] else 1.0, coef)
             if sr:
-                torch.ops.tamd.mt_adamw_step_sr_(tab.table, tab.n, tab.chunks, float(lr), float(b1), float(b2),
-                                                 float(group["eps"]), float(group["weight_decay"]), t,
-                                                 -1.0 if group["maximize"] else 1.0, coef, _DTYPE_CODE[mdt])
+                torch.ops.tamd.mt_adamw_step_sr_(*args, _DTYPE_CODE[mdt])
             else:
-                torch.ops.tamd.mt_adamw_step_(tab.table, tab.n, tab.chunks, float(lr), float(b1), float(b2),
-                                              float(group["eps"]), float(group["weight_decay"]), t,
-                                              -1.0 if group["maximize"] else 1.0, coef, _DTYPE_CODE[dt], _DTYPE_CODE[mdt])
+                torch.ops.tamd.mt_adamw_step_(*args, _DTYPE_CODE[dt], _DTYPE_CODE[mdt])
         for k in [k for k in self._tables if k not in live]:
             del self._tables[k]
         return loss
