@@ -23,12 +23,13 @@ int tamd_gemm_set_clock_buffer(void* buf);
  * the grid's timeline: ramp, tail, whether the XCDs finish together (tools/gemm_timeline.py); NULL switches it off */
 int tamd_gemm_set_timeline_buffer(void* buf);
 
-/* Ablation / A-B selector for the full-line GEMM kernel (plain epilogue).  Row-major operands, WRONG RESULTS by design:
- * bit mask 1 no LDS-DMA after the prologue, 2 no LDS fragment reads, 4 no vmcnt wait at the hand-off, 8 no barrier
- * (supported: 1, 2, 4, 8, 12, 15; tools/gemm_fl_dbg.py).  CORRECT, bit-identical results, every layout: 32 = the early
- * LDS-DMA piece placement (the product schedule whenever A is row-major), 128 = the late placement (the product
- * schedule of the dW layout).  tools/gemm_piece_ab.py */
+/* Schedule selector of the full-line GEMM kernel (plain epilogue; every layout; bit-identical results): 0 = the product's
+ * choice by layout, 32 = the one-barrier ring with the early LDS-DMA piece placement, 128 = the ring with the late
+ * placement, 1024 = the three-barrier loop, 2048 = the ring with the layout's own placement.  Any other value returns
+ * TAMD_E_ARG and leaves the selector as it was (the arms that were measured and retired: profiles/gemm_fl_retired_arms.patch).
+ * TAMD_GEMM_DBG in the environment sets the initial value.  tools/gemm_piece_ab.py, tools/gemm_power.py */
 int tamd_gemm_set_dbg(int dbg);
+int tamd_gemm_get_dbg(void); /* the selector's current value */
 
 /* Phase trace of the attention forward kernel: while `buf` (uint64[32], device memory) is set, workgroup 0 of every
  * tamd_attn_fwd launch stores per-wave shader-clock sums of its tile-loop phases at buf[wave * 8 + phase]

@@ -4,7 +4,6 @@ unless the op's output rounding dominates (then 2^-8 relative = one bf16 ulp); i
 (embedding gather, label handling) are bit-exact.  Each test runs twice: under the CPU execution model
 (`emu`, not gpu) and on the MI355X (`hip`, gpu)."""
 import math
-import os
 
 import pytest
 import torch
@@ -969,35 +968,40 @@ def test_residual_epilogue_on_a_small_grid_goes_through_split_k(env):
 
 
 def test_gemm_piece_placements_are_bit_identical(env):
-    """The two LDS-DMA piece placements of the full-line GEMM kernel -- early (the product schedule whenever A is row-major:
-    forward and dX) and late (dW) -- compute the same bits in every layout; the diagnostic entry point
-    tamd_gemm_set_dbg(32 / 128) selects the other one (tools/gemm_piece_ab.py measures them), 64 / 256 / 512 the experimental
-    placements of round 5 (pieces first; the hand-off split into its write-after-read and its landed-data half)."""
+    """The schedules of the full-line GEMM kernel -- the three-barrier loop (the product schedule of forward and dW) and the
+    one-barrier ring with the early (dX) or the late LDS-DMA piece placement -- compute the same bits in every layout; the
+    diagnostic entry point tamd_gemm_set_dbg(32 / 128 / 1024 / 2048) forces one of them (tools/gemm_piece_ab.py measures them)
+    and refuses every other value.  The one- and three-stage products pin the prologue's park() at j == nst and the odd-count
+    tail of the three-barrier loop, with ragged last tiles in M and N."""
     lib = ops.backend().lib
     if not hasattr(lib, "tamd_gemm_set_dbg"):
         pytest.skip("needs the diagnostic entry points (CPU execution model or libtamd_diag.so)")
-    if not env.big:
-        os.environ["TAMD_PERSIST_GRID"] = "2"  # (read once by the diagnostic build: three tiles per workgroup of the persistent walk)
-    torch.manual_seed(61)
-    dev = env.device
-    m, n, k = (1536, 1024, 1280) if env.big else (512, 520, 768)  # (a multiple of four 64-deep stages: DBG 1024)
-    x = torch.randn(m, k).bfloat16().to(dev)
-    w = (torch.randn(n, k) * k ** -0.5).bfloat16().to(dev)
-    layouts = [((x, w), {}), ((x, w.t().contiguous()), {"b_kn": True}),
-               ((x.t().contiguous(), w.t().contiguous()), {"a_km": True, "b_kn": True})]
-    ref = x.float() @ w.float().t()
-    try:
-        for args, kw in layouts:
-            plain = ops.raw_gemm(*args, sched="fl", **kw)
-            assert rel_err(plain, ref) < 0.0036
-            # (64 / 256 / 512: the round-5 placements, row-major A only -- the split hand-off of 512 is what the adversarial LDS-DMA
-            # timing of the CPU model is for; 1024: round 6, hipBLASLt's three-barrier loop structure, every layout)
-            for dbg in (32, 128, 64, 256, 512, 1024, 2048, 1024 + 4096, 1024 + 8192, 1024 + 16384, 32768):  # (32768: the persistent walk)  # (2048: the one-barrier ring forced where three barriers are the product)
-                lib.tamd_gemm_set_dbg(dbg)
-                assert torch.equal(ops.raw_gemm(*args, sched="fl", **kw), plain), (kw, dbg)
-                lib.tamd_gemm_set_dbg(0)
+    try:  # a retired arm is refused and the selector stays where it was
+        assert lib.tamd_gemm_set_dbg(1024) == 0 and lib.tamd_gemm_get_dbg() == 1024
+        assert lib.tamd_gemm_set_dbg(64) != 0 and lib.tamd_gemm_get_dbg() == 1024
     finally:
         lib.tamd_gemm_set_dbg(0)
+    assert lib.tamd_gemm_get_dbg() == 0
+    torch.manual_seed(61)
+    dev = env.device
+    for m, n, k in [(1536, 1024, 1280) if env.big else (512, 520, 768), (264, 520, 64), (264, 520, 192)]:
+        x = torch.randn(m, k).bfloat16().to(dev)
+        w = (torch.randn(n, k) * k ** -0.5).bfloat16().to(dev)
+        layouts = [((x, w), {}), ((x, w.t().contiguous()), {"b_kn": True}),
+                   ((x.t().contiguous(), w.t().contiguous()), {"a_km": True, "b_kn": True})]
+        ref = x.float() @ w.float().t()
+        try:
+            for args, kw in layouts:
+                plain = ops.raw_gemm(*args, sched="fl", **kw)
+                assert rel_err(plain, ref) < 0.0036
+                # (32 / 128: the ring with the early / late placement; 1024: the three-barrier loop; 2048: the ring forced where
+                # three barriers are the product)
+                for dbg in (32, 128, 1024, 2048):
+                    assert lib.tamd_gemm_set_dbg(dbg) == 0
+                    assert torch.equal(ops.raw_gemm(*args, sched="fl", **kw), plain), ((m, n, k), kw, dbg)
+                    lib.tamd_gemm_set_dbg(0)
+        finally:
+            lib.tamd_gemm_set_dbg(0)
 
 
 # ---- round 4: the bert-base fusions (pre-scaled query columns, bias gradients

@@ -102,13 +102,13 @@ def gen(t):
         raise ValueError(err)
     k0, k1 = [], []
     for j, p in enumerate(t["xr"]):
-        k0.append((p, f"fx[1][{j}] = frag_a4(sa, 1, {j});"))
+        k0.append((p, f"fx[1][{j}] = frag_a_untracked(sa, 1, {j});"))
     k0.append((t["bar1"] - 1, "wait_lgkmcnt0();"))
     k0.append((t["bar1"], "raw_barrier();"))
     for j, p in enumerate(t["ap"]):
         k0.append((p, f"issue({j}, sa);"))
     for j, p in enumerate(t["yr"]):
-        k0.append((p, f"fw[1][{j}] = frag_b4(sb, 1, {j});"))
+        k0.append((p, f"fw[1][{j}] = frag_b_untracked(sb, 1, {j});"))
     k0.append((t["bar2"] - 1, "wait_lgkmcnt0();"))
     k0.append((t["bar2"], "raw_barrier();"))
     nb = 0
@@ -125,9 +125,9 @@ def gen(t):
     k1.append((t["bar3"] - 1, f"wait_vmcnt<{inflight}>();"))
     k1.append((t["bar3"], "raw_barrier();"))
     for j, p in enumerate(t["xr1"]):
-        k1.append((p, f"fx[0][{j}] = frag_a4(na, 0, {j});"))
+        k1.append((p, f"fx[0][{j}] = frag_a_untracked(na, 0, {j});"))
     for j, p in enumerate(t["yr1"]):
-        k1.append((p, f"fw[0][{j}] = frag_b4(nbs, 0, {j});"))
+        k1.append((p, f"fw[0][{j}] = frag_b_untracked(nbs, 0, {j});"))
 
     def chain(acts):
         return " \\\n".join(f"  if constexpr (i == {p}) {{ {code} }}" for p, code in sorted(acts))

@@ -1,11 +1,13 @@
-"""A/B of the two LDS-DMA piece placements of the full-line GEMM kernel on the Llama-3-8B shapes, interleaved rounds in one
-process (TFLOP/s per arm and round):
+"""A/B of the schedules of the full-line GEMM kernel on the Llama-3-8B shapes, interleaved rounds in one process (TFLOP/s per
+arm and round):
 
-  fl              the product kernel (early pieces whenever A is row-major: forward and dX; late for dW)
-  early / late    the other placement (diagnostic library: tamd_gemm_set_dbg 32 / 128)
+  fl              the product kernel (three-barrier loop for forward and dW, one-barrier ring with early pieces for dX)
+  early / late    the one-barrier ring with the early / late LDS-DMA piece placement (diagnostic library: tamd_gemm_set_dbg 32 / 128)
+  b3 / b1         --three-barrier: the three-barrier loop / the one-barrier ring, forced in every layout (1024 / 2048)
 
 (profiles/r03b_gemm_persist_ab.jsonl was written by this tool when it still carried the two arms of the persistent,
-XCD-aligned walk -- profiles/r03b_gemm_persist.patch.)
+XCD-aligned walk -- profiles/r03b_gemm_persist.patch; the arms p1 p2 p3 b3p b3c b3s pw of rounds 5 and 6 --
+profiles/gemm_fl_retired_arms.patch.)
 
 Split-K products (q|k|v and down dW) go through tamd_gemm_ws with the workspace the policy asks for.
 
@@ -29,7 +31,6 @@ ap.add_argument("--iters", type=int, default=6)
 ap.add_argument("--shapes", default="qkv,o_proj,gate_up,down,lm_head")
 ap.add_argument("--legs", default="fwd,dX,dW")
 ap.add_argument("--no-diag", action="store_true", help="product library only (no early / late arms)")
-ap.add_argument("--placements", action="store_true", help="also the round-5 placements (tamd_gemm_set_dbg 64 / 256 / 512)")
 ap.add_argument("--three-barrier", action="store_true", help="round 6: hipBLASLt's loop structure (tamd_gemm_set_dbg 1024), every layout")
 ap.add_argument("--only", default="", help="comma-separated arms to keep beside fl (e.g. b3)")
 args = ap.parse_args()
@@ -78,10 +79,8 @@ for name in args.shapes.split(","):
             arms.append("early" if lay == 3 else "late")
             if lay != 3:
                 arms.append("early")  # (forward layout: the product schedule until round 5; dX: still the product schedule)
-            if lay != 3 and args.placements:  # round 5: pieces behind the even pairs / pieces first / pieces first + split hand-off
-                arms += ["p1", "p2", "p3"]
             if args.three_barrier:
-                arms += ["b3", "b1", "b3p", "b3s", "b3c", "pw"]  # (three barriers (vendor table, one MFMA per gap) / the one-barrier ring, forced: one of them is what "fl" runs; the table rounded to MFMA pairs / SPREAD)
+                arms += ["b3", "b1"]  # (three barriers / the one-barrier ring, forced: one of them is what "fl" runs)
             if args.only:
                 arms = ["fl"] + [c for c in arms[1:] if c in args.only.split(",")]
         res = {c: [] for c in arms}
@@ -89,7 +88,7 @@ for name in args.shapes.split(","):
         for rnd in range(args.rounds):
             for c in arms:
                 if lib is not None:
-                    lib.tamd_gemm_set_dbg({"late": 128, "early": 32, "p1": 64, "p2": 256, "p3": 512, "b3": 1024, "b1": 2048, "b3p": 1024 + 4096, "b3c": 1024 + 16384, "b3s": 1024 + 8192}.get(c, 0))
+                    lib.tamd_gemm_set_dbg({"late": 128, "early": 32, "b3": 1024, "b1": 2048}.get(c, 0))
                 flags = lay
                 fn = lambda: gemm(a, b, flags, gm, gn, gk, out, ws)  # noqa: E731
                 res[c].append(round(2.0 * gm * gn * gk / time_ms(fn) / 1e9))

@@ -7,8 +7,9 @@ with the srcC chains; the dropout variants 1206 -> 806 with one hash per 2 x 2 b
         -Rpass-analysis=kernel-resource-usage transformers_amd/csrc/attention_bwd_dkdv.hip -o /tmp/dkdv.s 2> /tmp/dkdv.rpass
   python tools/isa_count.py /tmp/dkdv.s attn_bwd_dkdv_kernelINS_6bf16_tELi128ELb1ELb0ELb0ELi0ELb0 [-v] [--min-mfma 8]
 
-(the second argument is a substring of the kernel's mangled name; -v lists the VALU opcodes of each block; registers,
-spills and occupancy are in the .rpass file)."""
+(the second argument is a substring of the kernel's mangled name; -v lists the VALU opcodes of each block; --ops prints the
+opcode sequence of each block, one per line, so that two listings can be diffed; registers, spills and occupancy are in the
+.rpass file)."""
 import collections
 import sys
 
@@ -62,6 +63,8 @@ def main():
         h = collections.Counter(cls(o) for o in ops)
         if h["mfma"] >= min_mfma:
             print(b, len(ops), dict(h))
+            if "--ops" in sys.argv:
+                print("\n".join("    " + o for o in ops))
             if "-v" in sys.argv:
                 print("   ", collections.Counter(o for o in ops if cls(o) == "valu").most_common(25))
 

@@ -108,6 +108,7 @@ DIAG_SIGNATURES = {
     "tamd_gemm_set_clock_buffer": (c_int, [P]),
     "tamd_gemm_set_timeline_buffer": (c_int, [P]),
     "tamd_gemm_set_dbg": (c_int, [c_int]),
+    "tamd_gemm_get_dbg": (c_int, []),
     "tamd_attn_set_trace": (c_int, [P]),
     "tamd_mfma_power": (c_int, [P, c_int, c_int, c_int, P, P, P]),
     "tamd_probe": (c_int, [P, P, P, c_int, c_int, P]),

@@ -36,6 +36,7 @@
 //   gemm_sm_kernel  128 x 128 tile, 4 waves x (64 x 64) on v_mfma_f32_32x32x16, two workgroups per CU: forward products whose
 //                   256 x 256 grid cannot spread over the GPU (a CLIP tower's 577 tokens)
 #include <limits.h>
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <type_traits>
@@ -735,14 +736,6 @@ __device__ __forceinline__ void mfma16_inplace(f32x4& c, const u32x4& a, const u
   c = mfma16<T>(a, b, c);
 #endif
 }
-// counted LDS wait (the fragment reads of the three-barrier loop are issued behind the compiler's back; LDS operations return in
-// order, so "at most N outstanding" = "everything but the N youngest reads has arrived")
-template <int N>
-__device__ __forceinline__ void wait_lgkmcnt_le() {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-#endif
-}
 __device__ __forceinline__ void mfma_drain() {
 #if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
@@ -772,37 +765,51 @@ __device__ __forceinline__ unsigned fl_frag_off_km(int c16, int lane) {
   return (unsigned)(8 * g4 + kq) * 512u + (unsigned)slot * 16u + (unsigned)(col & 7) * 2u;
 }
 
-// DBG (diagnostic instantiations, built only with -DTAMD_DIAG into libtamd_diag.so; TAMD_GEMM_DBG=n): wrong results by
-// design -- 1 no LDS-DMA after the prologue, 2 no LDS fragment reads, 4 no vmcnt wait at the hand-off, 8 no barrier; correct,
-// bit-identical results -- 32 the early piece placement (below) in every layout, 128 the late placement (pieces behind
-// the odd MFMA pairs 17..31: the schedule of round 2) in every layout.
-// Piece placement (EARLY): the 8 LDS-DMA pieces of a k-step go out behind its MFMA pairs 2, 5, .. 23, the 16 fragment
+// SCHED: the K loop's schedule.  The product library instantiates kSchedAuto only; the diagnostic library (-DTAMD_DIAG,
+// libtamd_diag.so) can force one of the others for the plain epilogue (tamd_gemm_set_dbg, include/tamd_diag.h; TAMD_GEMM_DBG=n
+// in the environment).  Every schedule issues the same MFMAs in the same order: bit-identical results.
+constexpr int kSchedAuto = 0;             // by layout: the three-barrier loop when both operands have the same layout (forward,
+                                          // dW), the ring with the early placement for row-major A and k-major B (dX), the ring
+                                          // with the late placement for k-major A and row-major B
+constexpr int kSchedRingEarly = 32;       // one-barrier ring, early piece placement
+constexpr int kSchedRingLate = 128;       // one-barrier ring, late piece placement
+constexpr int kSchedThreeBarrier = 1024;  // three-barrier loop
+constexpr int kSchedRing = 2048;          // one-barrier ring with the layout's own placement (early iff A is row-major)
+// Piece placement of the ring (EARLY): the 8 LDS-DMA pieces of a k-step go out behind its MFMA pairs 2, 5, .. 23, the 16 fragment
 // reads of the next k-step on the pairs between them -- 23 MFMAs (~400 cycles) more on average for a piece to land
 // before the hand-off waits for it than behind the odd pairs 17..31 (hipBLASLt's gfx950 kernel gives its operands
 // 84-182 MFMAs).  Measured on MI355X (profiles/r03a_gemm_stagger_ab.jsonl, r03b_gemm_persist_ab.jsonl): +1.0 ... +2.6 %
 // on the five forward shapes of Llama-3-8B and +0.7 ... +2.9 % on their dX products (lm_head dX, 2004 stages: +10 %), but
-// -3 ... -4 % on the long dW products -- so it is the product schedule whenever A is row-major (forward and dX), and the
-// late placement stays for dW (both operands k-major).  The same A/B buried two other differences to
-// hipBLASLt's loop: a staggered, wrapping K start per workgroup (13 configurations: -1 ... +2 %, no pattern) and a
+// -3 ... -4 % on the long dW products -- so the ring places early whenever A is row-major, and the late placement (pieces
+// behind the odd MFMA pairs 17..31: the schedule of round 2) stays for k-major A.  The same A/B buried two other differences
+// to hipBLASLt's loop: a staggered, wrapping K start per workgroup (13 configurations: -1 ... +2 %, no pattern) and a
 // second barrier per k-step (+-0.5 %).
-// (Round 3 also measured a persistent walk -- one workgroup per CU, the XCD's workgroups starting every dispatch round
-// together through an arrival counter, optionally re-aligned every 64 stages inside a tile -- against the drift of the
-// long-K products: it took the L2 hit rate of the gate|up dX / dW from 74 / 62 % to the 81 % of the 8 x 4 patch and their
-// fabric traffic to the patch floor (11.2 GB), and bought nothing: 1492 vs 1498 TFLOP/s with aligned rounds, -22 % with the
-// hand-shakes.  The L2 misses of the long-K products are not what bounds them.  profiles/r03b_gemm_persist_ab.jsonl,
-// r03b_gemm_persist_pmc.txt; the code: profiles/r03b_gemm_persist.patch.)
+// The three-barrier loop (round 6) = the loop STRUCTURE of hipBLASLt's MT256x256x64_MI16x16x1 kernel, read off its disassembly
+// (profiles/r06_hipblaslt_loop.md): LDS double-buffered by whole stages (A_s, B_s in half-slots 2(s&1), 2(s&1)+1), three
+// barriers per stage, each in the middle of an MFMA run behind a wait that is long satisfied --
+//   k-step 0: the 8 A fragments of k-step 1 behind MFMAs 1,3..15 | lgkmcnt(0) 21, BARRIER 22: A_s is read by everybody |
+//             A_{s+2} pieces 0..4 behind 23,26..35 with the 8 B fragments of k-step 1 behind 25,28,31,34,37,39,41,43 |
+//             lgkmcnt(0) 51, BARRIER 52: B_s is read | A_{s+2} pieces 5..7 behind 53,56,59 | B_{s+2} piece 0 behind 62
+//   k-step 1: B_{s+2} pieces 1..4 behind 1,22,24,26 | vmcnt(13) 28, BARRIER 29: stage s+1 has landed for everybody |
+//             the 16 fragments of k-step 0 of stage s+1 behind 30..60, B_{s+2} pieces 5..7 behind 33,37,61 | lgkmcnt(0) 63
+// -- the vendor table at its own granularity: ONE MFMA per gap, at most one feed instruction behind it (kfine_0 / kfine_1).
+// Measured on MI355X against the one-barrier ring, interleaved, bit-identical (profiles/r06b_gemm_piece_ab.jsonl): forward
+// q|k|v +2.9 %, o_proj +2.3 %, gate|up +1.8 %, down -0.1 %; dW o_proj +1.9 %, gate|up +2.8 %; dX -1.2 ... +1.0 %; the one-MFMA
+// gaps against the table rounded to MFMA pairs (r06g_, r06h_gemm_piece_ab.jsonl): forward +0.9 / +0.5 / +0.3 / 0.0 % (q|k|v,
+// o_proj, gate|up, down), dW o_proj +1.9 %, gate|up +2.2 %.  It is the product schedule of the forward layout (both operands
+// row-major) and of dW (both k-major) since round 6; dX (row-major A, k-major B) keeps the one-barrier ring.
+// Measured and retired (none promoted; the code of all but the first: profiles/gemm_fl_retired_arms.patch):
+//   * XCD-aligned persistent walk of round 3: level to -22 % -- r03b_gemm_persist_ab.jsonl, r03b_gemm_persist_pmc.txt; code: r03b_gemm_persist.patch
+//   * wrong-result ablations (no LDS-DMA / no fragment reads / no vmcnt wait / no barrier): r01_gemm_fl_ablation.jsonl, r02j_gemm_fl_ablation_16x16x32.jsonl
+//   * round-5 ring placements (pieces on the even pairs / pieces first / pieces first + split hand-off): +-0.2 %, -1 ... -2.5 %, -2 ... -4 % -- r05b_, r05c_gemm_piece_ab.jsonl
+//   * three-barrier table rounded to MFMA pairs: -0.3 ... -2.2 % -- r06g_, r06h_gemm_piece_ab.jsonl
+//   * one memory instruction per gap with early B pieces: -0.5 ... -4.4 % -- r06g_, r06h_gemm_piece_ab.jsonl
+//   * counted lgkmcnt at the stage boundary: +-1 % -- r06g_, r06h_gemm_piece_ab.jsonl
+//   * persistent walk with the next tile's stage 0 requested under the way out: -1.4 ... +1.2 % -- r06m_gemm_piece_ab.jsonl
 // (the kernel body: `vbid` = the workgroup's index inside ITS product -- blockIdx.x for gemm_fl_kernel, the index behind the
 // product's first workgroup for gemm_fl_group_kernel)
-template <typename T, bool A_KM, bool B_KN, int EPI, int ACT, int DBG>
-// `pstride` (PERSIST instantiations, DBG bit 32768): the workgroup walks the tiles vbid, vbid + pstride, ... and requests stage 0 of
-// its NEXT tile before it starts the way out of the current one, so that the first-stage latency of a tile (and the dispatch of a
-// fresh workgroup) hides under the way out: the two-point fit of profiles/r06d_gemm_vs_hipblaslt_pmc.md prices prologue + way out
-// at ~4 stage-times per tile -- 6 % of a 64-stage tile.  The way out then stages above the first LDS buffer (offset 64 KiB).
-// Measured (profiles/r06m_gemm_piece_ab.jsonl; bit-identical; CPU model: three tiles per workgroup under adversarial LDS-DMA
-// timing): forward q|k|v +0.9 %, o_proj -1.4 %, gate|up +0.2 %, down -0.2 %; dW o_proj +1.2 %, gate|up +0.5 % -- level, like the
-// persistent walks of rounds 2 and 3.  Under the board's power cap (profiles/r06j_gemm_power.jsonl) an idle gap between tiles is
-// not lost time: the cycles it frees come back as clock.  Diagnostic library only (tamd_gemm_set_dbg(32768)).
-__device__ __forceinline__ void gemm_fl_body(const GemmArgs& g, const int vbid, const int pstride = 0) {
+template <typename T, bool A_KM, bool B_KN, int EPI, int ACT, int SCHED>
+__device__ __forceinline__ void gemm_fl_body(const GemmArgs& g, const int vbid) {
   TAMD_DYN_SMEM(smem);
   const int lane = threadIdx.x & 63;
   const int wave = wave_id_uniform();
@@ -810,12 +817,14 @@ __device__ __forceinline__ void gemm_fl_body(const GemmArgs& g, const int vbid, 
   const int g4 = lane >> 4, l15 = lane & 15;
   TAMD_TIMELINE_BEGIN
   TAMD_CLOCK_BEGIN
-  constexpr bool PERSIST = (DBG & 32768) != 0;
-  static_assert(!PERSIST || (EPI != kEpiSplitK && EPI != kEpiSwiGLU && A_KM == B_KN), "persistent walk: three-barrier layouts, plain ways out");
+  static_assert(SCHED == kSchedAuto || SCHED == kSchedRingEarly || SCHED == kSchedRingLate || SCHED == kSchedThreeBarrier ||
+                    SCHED == kSchedRing, "gemm_fl_body: unknown schedule");
+  constexpr bool THREE_BARRIER = SCHED == kSchedThreeBarrier || (SCHED == kSchedAuto && A_KM == B_KN);
+  constexpr bool EARLY = SCHED == kSchedRingEarly || (SCHED != kSchedRingLate && !A_KM);  // the ring's piece placement
   int tile_m, tile_n;
   const int split = (EPI == kEpiSplitK) ? (int)((unsigned)vbid % (unsigned)g.splits) : 0;
   gemm_tile_of_block(g, (EPI == kEpiSplitK) ? (int)((unsigned)vbid / (unsigned)g.splits) : vbid, &tile_m, &tile_n);
-  int64_t m0 = (int64_t)tile_m * kBM, n0 = (int64_t)tile_n * kBN;
+  const int64_t m0 = (int64_t)tile_m * kBM, n0 = (int64_t)tile_n * kBN;
   const T* A = reinterpret_cast<const T*>(g.A);
   const T* B = reinterpret_cast<const T*>(g.B);
 
@@ -839,33 +848,37 @@ __device__ __forceinline__ void gemm_fl_body(const GemmArgs& g, const int vbid, 
   unsigned voff[16];  // byte offset from the operand base + 4096 - 1024*(piece & 3)
   int64_t kinc_a, kinc_b;  // bytes per stage; 0 once parked
   const char *base_a, *base_b;
-  auto tile_sources = [&]() __attribute__((always_inline)) {  // bases and lane offsets of the tile at (m0, n0)
-  kinc_a = A_KM ? (int64_t)kXK * g.lda * 2 : kXK * 2;
-  kinc_b = B_KN ? (int64_t)kXK * g.ldb * 2 : kXK * 2;
-  // operand bases (tile origin - 4096 B so that no lane offset goes negative after the immediate is taken out)
-  base_a = (const char*)(A_KM ? A + m0 : A + m0 * g.lda) - 4096 + (int64_t)st0 * kinc_a;
-  const int64_t nb0 = (EPI == kEpiSwiGLU) ? 0 : n0;  // SwiGLU: per-lane offsets address the whole fused weight
-  base_b = (const char*)(B_KN ? B + n0 : B + nb0 * g.ldb) - 4096 + (int64_t)st0 * kinc_b;
+  // (a lambda called once, not straight-line code: without it the compiler orders the prologue's per-lane offset arithmetic
+  // differently -- 18 ... 218 instructions of every instantiation -- and the dW gate|up product and the fused SwiGLU forward of
+  // Llama-3-8B measured 0.5 ... 1.7 % slower twice, profiles/gemm_fl_retire_ab.jsonl; with it the opcode sequence of every
+  // instantiation is the one from before the persistent walk left the body, profiles/gemm_fl_retire_isa.md)
+  auto tile_sources = [&]() __attribute__((always_inline)) {
+    kinc_a = A_KM ? (int64_t)kXK * g.lda * 2 : kXK * 2;
+    kinc_b = B_KN ? (int64_t)kXK * g.ldb * 2 : kXK * 2;
+    // operand bases (tile origin - 4096 B so that no lane offset goes negative after the immediate is taken out)
+    base_a = (const char*)(A_KM ? A + m0 : A + m0 * g.lda) - 4096 + (int64_t)st0 * kinc_a;
+    const int64_t nb0 = (EPI == kEpiSwiGLU) ? 0 : n0;  // SwiGLU: per-lane offsets address the whole fused weight
+    base_b = (const char*)(B_KN ? B + n0 : B + nb0 * g.ldb) - 4096 + (int64_t)st0 * kinc_b;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int row = (wave * 8 + i) * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ ((row >> 1) & 7);
-    const int kr = (wave * 8 + i) * 2 + (lane >> 5);
-    const int col = ((lane & 31) ^ (((kr & 3) << 2) | (((kr >> 3) & 1) << 1))) * 8;
-    const int64_t gca = (m0 + col < g.M) ? m0 + col : g.M - 8;
-    const int64_t ra = (m0 + row < g.M) ? m0 + row : g.M - 1;
-    const int64_t gcb = (n0 + col < g.N) ? n0 + col : g.N - 8;
-    int64_t rb = (n0 + row < g.N) ? n0 + row : g.N - 1;
-    if (EPI == kEpiSwiGLU) {  // tile row -> row of the fused [gate ; up] weight (see gemm_epilogue_swiglu)
-      int64_t feat = (n0 >> 1) + ((row >> 6) << 5) + (row & 31);
-      if (feat >= g.n_half) feat = g.n_half - 1;
-      rb = ((row >> 5) & 1) * g.n_half + feat;
+    for (int i = 0; i < 8; ++i) {
+      const int row = (wave * 8 + i) * 8 + (lane >> 3);
+      const int c = (lane & 7) ^ ((row >> 1) & 7);
+      const int kr = (wave * 8 + i) * 2 + (lane >> 5);
+      const int col = ((lane & 31) ^ (((kr & 3) << 2) | (((kr >> 3) & 1) << 1))) * 8;
+      const int64_t gca = (m0 + col < g.M) ? m0 + col : g.M - 8;
+      const int64_t ra = (m0 + row < g.M) ? m0 + row : g.M - 1;
+      const int64_t gcb = (n0 + col < g.N) ? n0 + col : g.N - 8;
+      int64_t rb = (n0 + row < g.N) ? n0 + row : g.N - 1;
+      if (EPI == kEpiSwiGLU) {  // tile row -> row of the fused [gate ; up] weight (see gemm_epilogue_swiglu)
+        int64_t feat = (n0 >> 1) + ((row >> 6) << 5) + (row & 31);
+        if (feat >= g.n_half) feat = g.n_half - 1;
+        rb = ((row >> 5) & 1) * g.n_half + feat;
+      }
+      const int64_t oa = A_KM ? (int64_t)kr * g.lda + (gca - m0) : (ra - m0) * g.lda + c * 8;
+      const int64_t ob = B_KN ? (int64_t)kr * g.ldb + (gcb - n0) : (rb - nb0) * g.ldb + c * 8;
+      voff[i] = (unsigned)(oa * 2 + 4096 - (i & 3) * 1024);
+      voff[8 + i] = (unsigned)(ob * 2 + 4096 - (i & 3) * 1024);
     }
-    const int64_t oa = A_KM ? (int64_t)kr * g.lda + (gca - m0) : (ra - m0) * g.lda + c * 8;
-    const int64_t ob = B_KN ? (int64_t)kr * g.ldb + (gcb - n0) : (rb - nb0) * g.ldb + c * 8;
-    voff[i] = (unsigned)(oa * 2 + 4096 - (i & 3) * 1024);
-    voff[8 + i] = (unsigned)(ob * 2 + 4096 - (i & 3) * 1024);
-  }
   };
   tile_sources();
   // past the last stage: keep the load counts uniform and re-read the last valid stage (idempotent)
@@ -876,9 +889,7 @@ __device__ __forceinline__ void gemm_fl_body(const GemmArgs& g, const int vbid, 
     kinc_b = 0;
   };
   const unsigned piece0 = (unsigned)wave * 8192u;  // this wave's first piece inside an operand stage
-  bool dma_on = true;
   auto issue = [&](int p, int slot) __attribute__((always_inline)) {  // piece p (0..15) of this wave into half-slot `slot`
-    if ((DBG & 1) && !dma_on) return;
     const unsigned dst = (unsigned)slot * kXHalf + piece0 + (unsigned)((p & 7) >> 2) * 4096u;  // + immediate
     const char* base = (p < 8) ? base_a : base_b;
     switch (p & 3) {
@@ -929,7 +940,6 @@ __device__ __forceinline__ void gemm_fl_body(const GemmArgs& g, const int vbid, 
   // fragment read number r (0..15) of k-step q of stage slots (sa, sb) into buffer buf, in the order the MFMAs of the
   // next k-step want them: w0 x0 x1 .. x7 w1 .. w7
   auto rd1 = [&](int sa, int sb, int q, int buf, int r) __attribute__((always_inline)) {
-    if ((DBG & 2) && !dma_on) return;
     if (r == 0)
       fw[buf][0] = frag_b(sb, q, 0);
     else if (r <= 8)
@@ -944,31 +954,6 @@ __device__ __forceinline__ void gemm_fl_body(const GemmArgs& g, const int vbid, 
   // SIMD: nobody else fills it) never waits behind a clump of LDS / LDS-DMA issues.  EARLY: of the pairs 0..23 every
   // third carries a piece, the other two a fragment read (the last read 9 pairs ahead of the hand-off's lgkmcnt(0));
   // otherwise reads behind the pairs 0..15, pieces behind the odd pairs 17..31.
-  constexpr bool EARLY = (!A_KM || (DBG & 32)) && !(DBG & 128);
-  // diagnostic placements (round 5, after the PMC side-by-side with hipBLASLt's kernel showed our waves parked at the hand-off
-  // twice as long as theirs, profiles/r05a_gemm_vs_hipblaslt_pmc.md): 1 = pieces behind the even pairs 0..14, reads behind the odd
-  // pairs 1..15 and 16..23; 2 = all 8 pieces behind the pairs 0..7, reads behind 8..23; 3 = as 2, and the hand-off is split --
-  // only the write-after-read half (lgkmcnt(0) + barrier) stays at the k-step boundary, the wait for the landed stage
-  // (vmcnt(16) + barrier) moves behind the 8 pieces of k-step 1, in front of the first read of the new stage: the operand
-  // with the short lead (B) gets a whole stage (128-144 MFMAs instead of 82-124)
-  // Measured (profiles/r05b_gemm_piece_ab.jsonl, r05c_gemm_piece_ab.jsonl; interleaved, two MI355X boxes): placement 1 within
-  // +-0.2 % of the product schedule on the five forward shapes over five rounds (the first box's +0...2.6 % over three rounds
-  // was noise), 2 -1 ... -2.5 %, 3 -2 ... -4 %: back-to-back LDS-DMA issues and a barrier inside the MFMA stream cost more
-  // than the longer lead buys.  The product schedule stays EARLY; the three stay selectable in the diagnostic library.
-  // 4 (round 6, DBG 1024) = the loop STRUCTURE of hipBLASLt's MT256x256x64_MI16x16x1 kernel, read off its disassembly
-  // (profiles/r06_hipblaslt_loop.md): LDS double-buffered by whole stages (A_s, B_s in half-slots 2(s&1), 2(s&1)+1), three
-  // barriers per stage, each in the middle of an MFMA run behind a wait that is long satisfied --
-  //   k-step 0: the 8 A fragments of k-step 1 behind MFMAs 1,3..15 | lgkmcnt(0) 21, BARRIER 22: A_s is read by everybody |
-  //             A_{s+2} pieces 0..4 behind 23,26..35 with the 8 B fragments of k-step 1 behind 25,28,31,34,37,39,41,43 |
-  //             lgkmcnt(0) 51, BARRIER 52: B_s is read | A_{s+2} pieces 5..7 behind 53,56,59 | B_{s+2} piece 0 behind 62
-  //   k-step 1: B_{s+2} pieces 1..4 behind 1,22,24,26 | vmcnt(13) 28, BARRIER 29: stage s+1 has landed for everybody |
-  //             the 16 fragments of k-step 0 of stage s+1 behind 30..60, B_{s+2} pieces 5..7 behind 33,37,61 | lgkmcnt(0) 63
-  // Same MFMA order, same summation order: bit-identical to the product schedule.
-  // Measured on MI355X against the one-barrier schedule, interleaved, bit-identical (profiles/r06b_gemm_piece_ab.jsonl): forward
-  // q|k|v +2.9 %, o_proj +2.3 %, gate|up +1.8 %, down -0.1 %; dW o_proj +1.9 %, gate|up +2.8 %; dX -1.2 ... +1.0 %.  It is the
-  // product schedule of the forward layout (both operands row-major) and of dW (both k-major) since round 6; dX (row-major A,
-  // k-major B) keeps the one-barrier ring.  DBG 1024 forces it in every layout, DBG 2048 forces the one-barrier ring.
-  constexpr int PLACE = (DBG & 64) ? 1 : ((DBG & 256) ? 2 : ((DBG & 512) ? 3 : (((DBG & 1024) || (A_KM == B_KN && !(DBG & (2048 | 32 | 128 | 15)))) ? 4 : 0)));
   auto kstep = [&](int buf, int ra, int rb, int rq, int pb, int ps) __attribute__((always_inline)) {
     kstep_open();
 #pragma unroll
@@ -977,20 +962,9 @@ __device__ __forceinline__ void gemm_fl_body(const GemmArgs& g, const int vbid, 
       acc[nb][mb] = mfma16<T>(fw[buf][nb], fx[buf][mb], acc[nb][mb]);
       acc[nb][mb + 1] = mfma16<T>(fw[buf][nb], fx[buf][mb + 1], acc[nb][mb + 1]);
       sched_fence();
-      if (PLACE == 1) {
-        if (p < 16 && (p & 1) == 0) issue(pb + (p >> 1), ps);
-        if (p < 16 && (p & 1) == 1) rd1(ra, rb, rq, buf ^ 1, p >> 1);
-        if (p >= 16 && p < 24) rd1(ra, rb, rq, buf ^ 1, p - 8);
-      } else if (PLACE >= 2) {
-        if (p < 8) issue(pb + p, ps);
-        if (PLACE == 3 && buf == 1 && p == 7) {  // the landed stage s+1: everybody's pieces (all but the 16 newest loads)
-          wait_vmcnt<16>();
-          raw_barrier();
-        }
-        if (p >= 8 && p < 24) rd1(ra, rb, rq, buf ^ 1, p - 8);
-      } else if (EARLY) {
-        if (p < 24 && p % 3 != 2) rd1(ra, rb, rq, buf ^ 1, p - p / 3);
+      if (EARLY) {  // (`issue` named before `rd1`: the order of the closure's captures decides the ring kernels' register numbers)
         if (p < 24 && p % 3 == 2) issue(pb + p / 3, ps);
+        if (p < 24 && p % 3 != 2) rd1(ra, rb, rq, buf ^ 1, p - p / 3);
       } else {
         if (p < 16) rd1(ra, rb, rq, buf ^ 1, p);
         if (p >= 16 && (p & 1)) issue(pb + ((p - 17) >> 1), ps);
@@ -998,113 +972,22 @@ __device__ __forceinline__ void gemm_fl_body(const GemmArgs& g, const int vbid, 
       sched_fence();
     }
   };
-  // ---- PLACE 4 (their instruction positions rounded to our MFMA pairs: a slot = behind MFMA 2p + 2)
-  // Fragment reads behind the compiler's back in every layout (`=v` pins the fragments to the VGPR half: with tracked reads the
-  // allocator put fragments into AGPRs and accumulators into VGPRs -- a copy in front of every MFMA, 56 spilled registers)
-  auto frag_a4 = [&](int slot, int q, int t) __attribute__((always_inline)) -> u32x4 {
+  // ---- the three-barrier loop
+  // Its fragment reads go behind the compiler's back in every layout (`=v` pins the fragments to the VGPR half: with tracked reads
+  // the allocator put fragments into AGPRs and accumulators into VGPRs -- a copy in front of every MFMA, 56 spilled registers)
+  auto frag_a_untracked = [&](int slot, int q, int t) __attribute__((always_inline)) -> u32x4 {
     if (A_KM) return frag_km((unsigned)slot * kXHalf + offx[A_KM ? t : 0], q * 16384);
     return lds_read16_untracked(smem, (unsigned)slot * kXHalf + offx[A_KM ? 0 : q], t * 2048);
   };
-  auto frag_b4 = [&](int slot, int q, int t) __attribute__((always_inline)) -> u32x4 {
+  auto frag_b_untracked = [&](int slot, int q, int t) __attribute__((always_inline)) -> u32x4 {
     if (B_KN) return frag_km((unsigned)slot * kXHalf + offw[B_KN ? t : 0], q * 16384);
     return lds_read16_untracked(smem, (unsigned)slot * kXHalf + offw[B_KN ? 0 : q], t * 2048);
   };
   // k-step 0 of the stage in LDS buffer b (half-slots 2b, 2b+1): fragments of its k-step 1 into register buffer 1, the pieces of
-  // stage s+2 into the same LDS buffer as the two barriers release its halves
-  auto kstep3_0 = [&](int b) __attribute__((always_inline)) {
-    const int sa = 2 * b, sb = 2 * b + 1;
-    wait_lgkmcnt0();  // (the fragments of this k-step: read behind the compiler's back)
-    sched_fence();
-#pragma unroll
-    for (int p = 0; p < 32; ++p) {
-      const int nb = p >> 2, mb = (p & 3) * 2;
-      mfma16_inplace<T>(acc[nb][mb], fw[0][nb], fx[0][mb]);
-      mfma16_inplace<T>(acc[nb][mb + 1], fw[0][nb], fx[0][mb + 1]);
-      sched_fence();
-      if (p < 8) fx[1][p] = frag_a4(sa, 1, p);
-      if (p == 10) {  // A_s is read by everybody
-        wait_lgkmcnt0();
-        raw_barrier();
-      }
-      if (p == 11) issue(0, sa);
-      if (p == 12) fw[1][0] = frag_b4(sb, 1, 0);
-      if (p == 12) issue(1, sa);
-      if (p == 13) fw[1][1] = frag_b4(sb, 1, 1);
-      if (p == 14) issue(2, sa);
-      if (p == 15) fw[1][2] = frag_b4(sb, 1, 2);
-      if (p == 15) issue(3, sa);
-      if (p == 16) fw[1][3] = frag_b4(sb, 1, 3);
-      if (p == 17) issue(4, sa);
-      if (p >= 18 && p <= 21) fw[1][p - 14] = frag_b4(sb, 1, p - 14);
-      if (p == 25) {  // B_s is read by everybody
-        wait_lgkmcnt0();
-        raw_barrier();
-      }
-      if (p == 26) issue(5, sa);
-      if (p == 27) issue(6, sa);
-      if (p == 29) issue(7, sa);
-      if (p == 30) issue(8, sb);
-      sched_fence();
-    }
-  };
-  // k-step 1: the rest of B_{s+2}; once stage s+1 has landed (LDS buffer b ^ 1) the fragments of its k-step 0 into register buffer 0
-  auto kstep3_1 = [&](int b) __attribute__((always_inline)) {
-    const int sb = 2 * b + 1, na = 2 * (b ^ 1), nbs = 2 * (b ^ 1) + 1;
-    wait_lgkmcnt0();  // (the fragments of this k-step: read behind the compiler's back)
-    sched_fence();
-#pragma unroll
-    for (int p = 0; p < 32; ++p) {
-      const int nb = p >> 2, mb = (p & 3) * 2;
-      mfma16_inplace<T>(acc[nb][mb], fw[1][nb], fx[1][mb]);
-      mfma16_inplace<T>(acc[nb][mb + 1], fw[1][nb], fx[1][mb + 1]);
-      sched_fence();
-      if (p == 0) issue(9, sb);
-      if (p >= 10 && p <= 12) issue(p, sb);
-      if (p == 13) {  // everything but this stage's 8 + 5 pieces: stage s+1 is in LDS, for everybody
-        wait_vmcnt<13>();
-        raw_barrier();
-      }
-      if (p == 14) fx[0][0] = frag_a4(na, 0, 0);
-      if (p == 15) fx[0][1] = frag_a4(na, 0, 1);
-      if (p == 15) fx[0][2] = frag_a4(na, 0, 2);
-      if (p == 16) fx[0][3] = frag_a4(na, 0, 3);
-      if (p == 16) issue(13, sb);
-      if (p == 17) fx[0][4] = frag_a4(na, 0, 4);
-      if (p == 18) issue(14, sb);
-      if (p == 19) fx[0][5] = frag_a4(na, 0, 5);
-      if (p == 19) fx[0][6] = frag_a4(na, 0, 6);
-      if (p == 20) fx[0][7] = frag_a4(na, 0, 7);
-      if (p == 20) fw[0][0] = frag_b4(nbs, 0, 0);
-      if (p == 21) fw[0][1] = frag_b4(nbs, 0, 1);
-      if (p == 22) fw[0][2] = frag_b4(nbs, 0, 2);
-      if (p == 24) fw[0][3] = frag_b4(nbs, 0, 3);
-      if (p == 25) fw[0][4] = frag_b4(nbs, 0, 4);
-      if (p == 26) fw[0][5] = frag_b4(nbs, 0, 5);
-      if (p == 28) fw[0][6] = frag_b4(nbs, 0, 6);
-      if (p == 29) fw[0][7] = frag_b4(nbs, 0, 7);
-      if (p == 30) issue(15, sb);
-      sched_fence();
-    }
-  };
-  // ---- the placements of this structure that were measured (profiles/r06b_, r06g_gemm_piece_ab.jsonl; interleaved, bit-identical):
-  //   FINE   : the vendor table at its own granularity -- ONE MFMA per gap, at most one feed instruction behind it.  THE PRODUCT
-  //            PLACEMENT: against the pair-rounded table forward +0.9 / +0.5 / +0.3 / 0.0 % (q|k|v, o_proj, gate|up, down), dW
-  //            o_proj +1.9 %, gate|up +2.2 %
-  //   pairs  : the same table rounded to our MFMA pairs (kstep3_*; DBG 4096): what first showed the structure pays
-  //   SPREAD : pairs, at most ONE memory instruction per gap, B_{s+2} in the first 13 gaps of k-step 1 (every other one) so that
-  //            the landed-data wait is vmcnt(16) and the 16 fragment reads of stage s+1 have gaps 14..29 to themselves (DBG 8192):
-  //            -0.5 ... -4.4 % -- an emptier gap is not what the loop was missing
-  constexpr bool SPREAD = (DBG & 8192) != 0, FINE = !(DBG & 4096) && !SPREAD;
-  // COUNTED (DBG 16384): the stage opens with lgkmcnt(4) instead of lgkmcnt(0) -- the four youngest reads (B fragments 4..7 of this
-  // k-step, requested behind MFMAs 51..60 of the previous stage) are first used by MFMA 33 and are covered by the lgkmcnt(0)
-  // in front of barrier (1), behind MFMA 21; B fragment 3 was requested 15 MFMAs ago.  (k-major fragments are two reads each.)
-  constexpr bool COUNTED = (DBG & 16384) != 0;
+  // stage s+2 into the same LDS buffer as the two barriers release its halves (`i` = the MFMA number in the table above gemm_fl_body)
   auto kfine_0 = [&](int b) __attribute__((always_inline)) {
     const int sa = 2 * b, sb = 2 * b + 1;
-    if (COUNTED)
-      wait_lgkmcnt_le<B_KN ? 8 : 4>();
-    else
-      wait_lgkmcnt0();
+    wait_lgkmcnt0();  // (the fragments of this k-step: read behind the compiler's back)
     sched_fence();
     static_for<1, 65>([&](auto I) __attribute__((always_inline)) {
       constexpr int i = decltype(I)::value;
@@ -1113,12 +996,12 @@ __device__ __forceinline__ void gemm_fl_body(const GemmArgs& g, const int vbid, 
 #ifdef TAMD_B3_TABLE  // (tools/b3_search.py: a generated table, force-included; the product has the vendor table below)
       TAMD_B3_K0_ACTIONS
 #else
-      if constexpr (i <= 15 && (i & 1)) fx[1][(i - 1) >> 1] = frag_a4(sa, 1, (i - 1) >> 1);
+      if constexpr (i <= 15 && (i & 1)) fx[1][(i - 1) >> 1] = frag_a_untracked(sa, 1, (i - 1) >> 1);
       if constexpr (i == 21) wait_lgkmcnt0();
       if constexpr (i == 22) raw_barrier();
       if constexpr (i >= 23 && i <= 35 && (i - 23) % 3 == 0) issue((i - 23) / 3, sa);
-      if constexpr (i >= 25 && i <= 37 && (i - 25) % 3 == 0) fw[1][(i - 25) / 3] = frag_b4(sb, 1, (i - 25) / 3);
-      if constexpr (i == 39 || i == 41 || i == 43) fw[1][5 + (i - 39) / 2] = frag_b4(sb, 1, 5 + (i - 39) / 2);
+      if constexpr (i >= 25 && i <= 37 && (i - 25) % 3 == 0) fw[1][(i - 25) / 3] = frag_b_untracked(sb, 1, (i - 25) / 3);
+      if constexpr (i == 39 || i == 41 || i == 43) fw[1][5 + (i - 39) / 2] = frag_b_untracked(sb, 1, 5 + (i - 39) / 2);
       if constexpr (i == 51) wait_lgkmcnt0();
       if constexpr (i == 52) raw_barrier();
       if constexpr (i == 53 || i == 56 || i == 59) issue(5 + (i - 53) / 3, sa);
@@ -1127,6 +1010,7 @@ __device__ __forceinline__ void gemm_fl_body(const GemmArgs& g, const int vbid, 
       sched_fence();
     });
   };
+  // k-step 1: the rest of B_{s+2}; once stage s+1 has landed (LDS buffer b ^ 1) the fragments of its k-step 0 into register buffer 0
   auto kfine_1 = [&](int b) __attribute__((always_inline)) {
     const int sb = 2 * b + 1, na = 2 * (b ^ 1), nbs = 2 * (b ^ 1) + 1;
     wait_lgkmcnt0();
@@ -1142,157 +1026,82 @@ __device__ __forceinline__ void gemm_fl_body(const GemmArgs& g, const int vbid, 
       if constexpr (i == 22 || i == 24 || i == 26) issue(10 + (i - 22) / 2, sb);
       if constexpr (i == 28) wait_vmcnt<13>();
       if constexpr (i == 29) raw_barrier();
-      if constexpr (i == 30 || i == 31 || i == 32) fx[0][i - 30] = frag_a4(na, 0, i - 30);
+      if constexpr (i == 30 || i == 31 || i == 32) fx[0][i - 30] = frag_a_untracked(na, 0, i - 30);
       if constexpr (i == 33) issue(13, sb);
-      if constexpr (i == 34 || i == 35) fx[0][i - 31] = frag_a4(na, 0, i - 31);
+      if constexpr (i == 34 || i == 35) fx[0][i - 31] = frag_a_untracked(na, 0, i - 31);
       if constexpr (i == 37) issue(14, sb);
-      if constexpr (i == 39 || i == 40 || i == 41) fx[0][i - 34] = frag_a4(na, 0, i - 34);
-      if constexpr (i == 42 || i == 43) fw[0][i - 42] = frag_b4(nbs, 0, i - 42);
-      if constexpr (i == 46) fw[0][2] = frag_b4(nbs, 0, 2);
-      if constexpr (i == 49) fw[0][3] = frag_b4(nbs, 0, 3);
-      if constexpr (i == 51) fw[0][4] = frag_b4(nbs, 0, 4);
-      if constexpr (i == 54) fw[0][5] = frag_b4(nbs, 0, 5);
-      if constexpr (i == 57) fw[0][6] = frag_b4(nbs, 0, 6);
-      if constexpr (i == 60) fw[0][7] = frag_b4(nbs, 0, 7);
+      if constexpr (i == 39 || i == 40 || i == 41) fx[0][i - 34] = frag_a_untracked(na, 0, i - 34);
+      if constexpr (i == 42 || i == 43) fw[0][i - 42] = frag_b_untracked(nbs, 0, i - 42);
+      if constexpr (i == 46) fw[0][2] = frag_b_untracked(nbs, 0, 2);
+      if constexpr (i == 49) fw[0][3] = frag_b_untracked(nbs, 0, 3);
+      if constexpr (i == 51) fw[0][4] = frag_b_untracked(nbs, 0, 4);
+      if constexpr (i == 54) fw[0][5] = frag_b_untracked(nbs, 0, 5);
+      if constexpr (i == 57) fw[0][6] = frag_b_untracked(nbs, 0, 6);
+      if constexpr (i == 60) fw[0][7] = frag_b_untracked(nbs, 0, 7);
       if constexpr (i == 61) issue(15, sb);
 #endif
       sched_fence();
     });
   };
-  auto kspread_0 = [&](int b) __attribute__((always_inline)) {
-    const int sa = 2 * b, sb = 2 * b + 1;
-    wait_lgkmcnt0();
-    sched_fence();
-#pragma unroll
-    for (int p = 0; p < 32; ++p) {
-      const int nb = p >> 2, mb = (p & 3) * 2;
-      mfma16_inplace<T>(acc[nb][mb], fw[0][nb], fx[0][mb]);
-      mfma16_inplace<T>(acc[nb][mb + 1], fw[0][nb], fx[0][mb + 1]);
-      sched_fence();
-      if (p < 8) fx[1][p] = frag_a4(sa, 1, p);
-      if (p == 10) {
-        wait_lgkmcnt0();
-        raw_barrier();
-      }
-      if (p >= 11 && p <= 19 && (p & 1)) issue((p - 11) >> 1, sa);              // 11 13 15 17 19: A pieces 0..4
-      if (p >= 12 && p <= 20 && !(p & 1)) fw[1][(p - 12) >> 1] = frag_b4(sb, 1, (p - 12) >> 1);  // 12 .. 20: B fragments 0..4
-      if (p >= 21 && p <= 23) fw[1][p - 16] = frag_b4(sb, 1, p - 16);             // 21 22 23: B fragments 5..7
-      if (p == 26) {
-        wait_lgkmcnt0();
-        raw_barrier();
-      }
-      if (p >= 27 && p <= 29) issue(p - 22, sa);  // A pieces 5..7
-      if (p == 30) issue(8, sb);
-      sched_fence();
-    }
-  };
-  auto kspread_1 = [&](int b) __attribute__((always_inline)) {
-    const int sb = 2 * b + 1, na = 2 * (b ^ 1), nbs = 2 * (b ^ 1) + 1;
-    wait_lgkmcnt0();
-    sched_fence();
-#pragma unroll
-    for (int p = 0; p < 32; ++p) {
-      const int nb = p >> 2, mb = (p & 3) * 2;
-      mfma16_inplace<T>(acc[nb][mb], fw[1][nb], fx[1][mb]);
-      mfma16_inplace<T>(acc[nb][mb + 1], fw[1][nb], fx[1][mb + 1]);
-      sched_fence();
-      if (p <= 12 && !(p & 1)) issue(9 + (p >> 1), sb);  // 0 2 .. 12: B pieces 1..7
-      if (p == 13) {  // all of this stage's 16 pieces may be in flight: everything older (stage s+1) has landed
-        wait_vmcnt<16>();
-        raw_barrier();
-      }
-      if (p >= 14 && p <= 21) fx[0][p - 14] = frag_a4(na, 0, p - 14);
-      if (p >= 22 && p <= 29) fw[0][p - 22] = frag_b4(nbs, 0, p - 22);
-      sched_fence();
-    }
-  };
-  int vb = vbid;     // PERSIST: the tile this workgroup is on
-  bool pre = false;  // PERSIST: stage 0 of the current tile was requested during the previous tile's way out
-  for (;;) {
-  if (PERSIST) {
-#pragma unroll
-    for (int nb = 0; nb < 8; ++nb)
-#pragma unroll
-      for (int mb = 0; mb < 8; ++mb) acc[nb][mb] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
   // prologue: A_0 B_0 A_1 B_1 into half-slots 0..3
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     if (j == nst) park();
-    if (!(PERSIST && j == 0 && pre)) {
 #pragma unroll
-      for (int p = 0; p < 16; ++p) issue(p, 2 * j + (p >> 3));
-    }
+    for (int p = 0; p < 16; ++p) issue(p, 2 * j + (p >> 3));
   }
-  if (PLACE == 4) {
+  if (THREE_BARRIER) {
     wait_vmcnt<16>();  // stage 0 has landed; stage 1 stays in flight (the first vmcnt(13) + barrier covers it)
     raw_barrier();
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
-      fx[0][t] = frag_a4(0, 0, t);
-      fw[0][t] = frag_b4(1, 0, t);
+      fx[0][t] = frag_a_untracked(0, 0, t);
+      fw[0][t] = frag_b_untracked(1, 0, t);
     }
-    wait_lgkmcnt0();  // (the loop's first stage may open with a counted wait that assumes the loop's own read order)
+    wait_lgkmcnt0();
     const int nst2 = nst & ~1;
     for (int s0 = 0; s0 < nst2; s0 += 2) {
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
         sched_fence();
         if (s0 + b + 2 == nst) park();
-        if (FINE) {
-          kfine_0(b);
-          kfine_1(b);
-        } else if (SPREAD) {
-          kspread_0(b);
-          kspread_1(b);
-        } else {
-          kstep3_0(b);
-          kstep3_1(b);
-        }
+        kfine_0(b);
+        kfine_1(b);
       }
     }
     if (nst & 1) {  // the last stage of an odd count (its parity is even: LDS buffer 0); stage s+2 is parked since s = nst - 2
       sched_fence();
-      if (FINE) {
-        kfine_0(0);
-        kfine_1(0);
-      } else if (SPREAD) {
-        kspread_0(0);
-        kspread_1(0);
-      } else {
-        kstep3_0(0);
-        kstep3_1(0);
-      }
+      kfine_0(0);
+      kfine_1(0);
     }
-  } else {
-  wait_vmcnt<0>();
-  raw_barrier();
+  } else {  // the one-barrier ring
+    wait_vmcnt<0>();
+    raw_barrier();
 #pragma unroll
-  for (int r = 0; r < 16; ++r) rd1(0, 1, 0, 0, r);
-  dma_on = false;
-  for (int s0 = 0; s0 < nst; s0 += kXSlots) {
+    for (int r = 0; r < 16; ++r) rd1(0, 1, 0, 0, r);
+    for (int s0 = 0; s0 < nst; s0 += kXSlots) {
 #pragma unroll
-    for (int u = 0; u < kXSlots; ++u) {
-      const int s = s0 + u;
-      if (s < nst) {
-        const int sa = (2 * u) % kXSlots, sb = (2 * u + 1) % kXSlots;        // A_s, B_s
-        const int sa1 = (2 * u + 2) % kXSlots, sb1 = (2 * u + 3) % kXSlots;  // A_{s+1}, B_{s+1}
-        const int sa2 = (2 * u + 4) % kXSlots;                               // A_{s+2} (= slot of B_{s-1})
-        const int sb2 = sa;                                                  // B_{s+2} (= slot of A_s)
-        sched_fence();
-        if (s + 2 == nst) park();
-        kstep(0, sa, sb, 1, 0, sa2);  // k-step 0 | second-half fragments of stage s | A_{s+2}
-        // hand-off: stage s+1 has landed for everybody; everybody's reads of stage s are in registers
-        if (!(DBG & 4) && PLACE != 3) wait_vmcnt<8>();  // own B_{s+1} (and the older A_{s+1}); the 8 newest (A_{s+2}) stay in flight
-        wait_lgkmcnt0();
-        if (!(DBG & 8)) raw_barrier();
-        sched_fence();
-        kstep(1, sa1, sb1, 0, 8, sb2);  // k-step 1 | first-half fragments of stage s+1 | B_{s+2} into the slot A_s vacated
+      for (int u = 0; u < kXSlots; ++u) {
+        const int s = s0 + u;
+        if (s < nst) {
+          const int sa = (2 * u) % kXSlots, sb = (2 * u + 1) % kXSlots;        // A_s, B_s
+          const int sa1 = (2 * u + 2) % kXSlots, sb1 = (2 * u + 3) % kXSlots;  // A_{s+1}, B_{s+1}
+          const int sa2 = (2 * u + 4) % kXSlots;                               // A_{s+2} (= slot of B_{s-1})
+          const int sb2 = sa;                                                  // B_{s+2} (= slot of A_s)
+          sched_fence();
+          if (s + 2 == nst) park();
+          kstep(0, sa, sb, 1, 0, sa2);  // k-step 0 | second-half fragments of stage s | A_{s+2}
+          // hand-off: stage s+1 has landed for everybody; everybody's reads of stage s are in registers
+          wait_vmcnt<8>();  // own B_{s+1} (and the older A_{s+1}); the 8 newest (A_{s+2}) stay in flight
+          wait_lgkmcnt0();
+          raw_barrier();
+          sched_fence();
+          kstep(1, sa1, sb1, 0, 8, sb2);  // k-step 1 | first-half fragments of stage s+1 | B_{s+2} into the slot A_s vacated
+        }
       }
     }
   }
-  }  // PLACE != 4
-  if (PLACE == 4) mfma_drain();
+  if (THREE_BARRIER) mfma_drain();
   wait_vmcnt<0>();
   wait_lgkmcnt0();
   raw_barrier();
@@ -1302,69 +1111,43 @@ __device__ __forceinline__ void gemm_fl_body(const GemmArgs& g, const int vbid, 
   // (checked per instantiation with tools/gemm_isa.sh and tests/test_isa_lint.py: since the buffer-addressed way out of round 5 no
   // full-line instantiation has scratch -- the k-major residual / accumulate ones used to spill 5-17 registers)
   const int elane = lane_id_mbcnt();
-  // PERSIST: the way out is for the tile at (em0, en0); the sources move on to the next tile first and its stage 0 is requested
-  // into LDS buffer 0 (half-slots 0, 1), which every wave has finished reading (the barrier above); the way out stages above it
-  const int64_t em0 = m0, en0 = n0;
-  constexpr unsigned kStageBase = PERSIST ? 2u * kXHalf : 0u;
-  if (PERSIST) {
-    const int nxt = vb + pstride;
-    pre = nxt < g.tiles_m * g.tiles_n;
-    if (pre) {
-      gemm_tile_of_block(g, nxt, &tile_m, &tile_n);
-      m0 = (int64_t)tile_m * kBM;
-      n0 = (int64_t)tile_n * kBN;
-      tile_sources();
-#pragma unroll
-      for (int p = 0; p < 16; ++p) issue(p, p >> 3);
-    }
-    vb = nxt;
-  }
   if (EPI == kEpiSplitK) {  // fp32 partial tile: lane = output row, 4 consecutive columns per accumulator block
     float* ws = g.ws + (int64_t)split * g.M * g.N;
     const int l15 = elane & 15, g4 = elane >> 4;
 #pragma unroll
     for (int mb = 0; mb < 8; ++mb) {
-      const int64_t m = em0 + wm * 128 + mb * 16 + l15;
+      const int64_t m = m0 + wm * 128 + mb * 16 + l15;
 #pragma unroll
       for (int nb = 0; nb < 8; ++nb) {
-        const int64_t n = en0 + wn * 128 + nb * 16 + 4 * g4;
+        const int64_t n = n0 + wn * 128 + nb * 16 + 4 * g4;
         if (m < g.M && n < g.N)
           st16(ws + m * g.N + n, u32x4{f32_as_u32(acc[nb][mb][0]), f32_as_u32(acc[nb][mb][1]), f32_as_u32(acc[nb][mb][2]),
                                        f32_as_u32(acc[nb][mb][3])});
       }
     }
   } else if (EPI == kEpiSwiGLU) {
-    gemm_epilogue_swiglu<T>(g, acc, smem, (unsigned)wave * (64u * (128 * 2 + 16) + 64u * (64 * 2 + 16)), em0 + wm * 128,
-                            (en0 >> 1) + wn * 64, elane);
+    gemm_epilogue_swiglu<T>(g, acc, smem, (unsigned)wave * (64u * (128 * 2 + 16) + 64u * (64 * 2 + 16)), m0 + wm * 128,
+                            (n0 >> 1) + wn * 64, elane);
   } else if (EPI == kEpiSwiGLUBwd) {
-    gemm_epilogue_swiglu_bwd<T>(g, acc, smem, kStageBase + (unsigned)wave * (64u * (4 * 32 * 2 + 16)), em0 + wm * 128, en0 + wn * 128,
+    gemm_epilogue_swiglu_bwd<T>(g, acc, smem, (unsigned)wave * (64u * (4 * 32 * 2 + 16)), m0 + wm * 128, n0 + wn * 128,
                                 elane);
   } else {
     constexpr int E2 = (EPI == kEpiSplitK || EPI == kEpiSwiGLU || EPI == kEpiSwiGLUBwd) ? TAMD_EPI_NONE : EPI;
     if (A_KM && B_KN && (EPI == TAMD_EPI_NONE || EPI == TAMD_EPI_ACCUM)) {  // dW: the tile's segment (wave-uniform selects;
       GemmArgs gs = g;                                                        // ONE epilogue instance: a second one spills)
-      gs.C = gemm_seg_base<T>(g, em0);
-      gemm_epilogue16<T, E2, ACT>(gs, acc, smem, kStageBase + (unsigned)wave * (64u * (4 * 32 * 2 + 16)), em0 + wm * 128, en0 + wn * 128,
+      gs.C = gemm_seg_base<T>(g, m0);
+      gemm_epilogue16<T, E2, ACT>(gs, acc, smem, (unsigned)wave * (64u * (4 * 32 * 2 + 16)), m0 + wm * 128, n0 + wn * 128,
                                   elane);
     } else {
-      gemm_epilogue16<T, E2, ACT>(g, acc, smem, kStageBase + (unsigned)wave * (64u * (4 * 32 * 2 + 16)), em0 + wm * 128, en0 + wn * 128,
+      gemm_epilogue16<T, E2, ACT>(g, acc, smem, (unsigned)wave * (64u * (4 * 32 * 2 + 16)), m0 + wm * 128, n0 + wn * 128,
                                   elane);
     }
   }
-  if (!PERSIST || !pre) break;
-  wait_lgkmcnt0();  // every wave is done with its staging area before stage 1 of the next tile lands in half-slots 2, 3
-  raw_barrier();
-  }  // for (;;)
   TAMD_TIMELINE_END
 }
-template <typename T, bool A_KM, bool B_KN, int EPI, int ACT, int DBG = 0>
+template <typename T, bool A_KM, bool B_KN, int EPI, int ACT, int SCHED = kSchedAuto>
 __global__ __launch_bounds__(kFlThreads, 1) void gemm_fl_kernel(GemmArgs g) {
-  gemm_fl_body<T, A_KM, B_KN, EPI, ACT, DBG>(g, (int)blockIdx.x);
-}
-// the persistent walk: one workgroup per CU (grid = the device's CU count, a multiple of 8 so that blockIdx & 7 stays the XCD)
-template <typename T, bool A_KM, bool B_KN, int EPI, int ACT, int DBG = 0>
-__global__ __launch_bounds__(kFlThreads, 1) void gemm_fl_persist_kernel(GemmArgs g) {
-  gemm_fl_body<T, A_KM, B_KN, EPI, ACT, DBG | 32768>(g, (int)blockIdx.x, (int)gridDim.x);
+  gemm_fl_body<T, A_KM, B_KN, EPI, ACT, SCHED>(g, (int)blockIdx.x);
 }
 
 // ============================================================================================ grouped launch
@@ -1387,7 +1170,7 @@ __global__ __launch_bounds__(kFlThreads, 1) void gemm_fl_group_kernel(GemmGroupA
   for (int j = 1; j < kGroupMax; ++j) i = (bid >= grp.start[j]) ? j : i;
   const int local = bid - grp.start[i];
   if (local >= grp.blocks[i]) return;
-  gemm_fl_body<T, A_KM, B_KN, EPI, TAMD_ACT_NONE, 0>(grp.p[i], local);  // (wave-uniform index into the kernel arguments)
+  gemm_fl_body<T, A_KM, B_KN, EPI, TAMD_ACT_NONE, kSchedAuto>(grp.p[i], local);  // (wave-uniform index into the kernel arguments)
 }
 
 // ============================================================================================ small tile
@@ -1570,17 +1353,39 @@ __global__ void splitk_reduce_group_kernel(ReduceGroupArgs r) {
 // ============================================================================================ host dispatch
 #ifndef TAMD_GEMM_KERNELS_ONLY  // (tools/gemm_isa.sh instantiates single kernels for a look at their ISA)
 #ifdef TAMD_DIAG
-// ablation selector of the diagnostic build (tamd_gemm_set_dbg, include/tamd_diag.h; TAMD_GEMM_DBG in the environment
-// sets the initial value): see the DBG template parameter of gemm_fl_kernel
+// schedule selector of the diagnostic build (tamd_gemm_set_dbg, include/tamd_diag.h; TAMD_GEMM_DBG in the environment
+// sets the initial value): see the SCHED template parameter of gemm_fl_kernel
+static bool gemm_sched_known(int v) {
+  return v == kSchedAuto || v == kSchedRingEarly || v == kSchedRingLate || v == kSchedThreeBarrier || v == kSchedRing;
+}
 static int g_gemm_dbg = -1;
 static int gemm_diag_dbg() {
   if (g_gemm_dbg < 0) {
     const char* e = getenv("TAMD_GEMM_DBG");
     g_gemm_dbg = e ? atoi(e) : 0;
+    if (!gemm_sched_known(g_gemm_dbg)) {
+      fprintf(stderr, "tamd: TAMD_GEMM_DBG=%s is not a schedule of gemm_fl_kernel (0, 32, 128, 1024, 2048): ignored\n", e);
+      g_gemm_dbg = 0;
+    }
   }
   return g_gemm_dbg;
 }
 #endif
+// the statement with `A_KM` / `B_KN` bound to the two layout bits of `flags` as compile-time constants
+#define TAMD_DISPATCH_LAYOUT(flags, ...)                  \
+  if (!((flags) & (TAMD_GEMM_A_KM | TAMD_GEMM_B_KN))) {   \
+    constexpr bool A_KM = false, B_KN = false;            \
+    __VA_ARGS__;                                          \
+  } else if (!((flags) & TAMD_GEMM_A_KM)) {               \
+    constexpr bool A_KM = false, B_KN = true;             \
+    __VA_ARGS__;                                          \
+  } else if ((flags) & TAMD_GEMM_B_KN) {                  \
+    constexpr bool A_KM = true, B_KN = true;              \
+    __VA_ARGS__;                                          \
+  } else {                                                \
+    constexpr bool A_KM = true, B_KN = false;             \
+    __VA_ARGS__;                                          \
+  }
 #define TAMD_EPI_SWITCH(LAUNCH)                                           \
   switch (epilogue) {                                                     \
     case TAMD_EPI_NONE: LAUNCH(TAMD_EPI_NONE, TAMD_ACT_NONE)              \
@@ -1611,85 +1416,26 @@ static int gemm_pp_launch_epi(const GemmArgs& g, int epilogue, int act, hipStrea
 
 template <typename T>
 static int gemm_pp_launch(const GemmArgs& g, int flags, int epilogue, int act, hipStream_t s) {
-  const bool akm = flags & TAMD_GEMM_A_KM, bkn = flags & TAMD_GEMM_B_KN;
-  if (!akm && !bkn) return gemm_pp_launch_epi<T, false, false>(g, epilogue, act, s);
-  if (!akm && bkn) return gemm_pp_launch_epi<T, false, true>(g, epilogue, act, s);
-  if (akm && bkn) return gemm_pp_launch_epi<T, true, true>(g, epilogue, act, s);
-  return gemm_pp_launch_epi<T, true, false>(g, epilogue, act, s);
+  TAMD_DISPATCH_LAYOUT(flags, return (gemm_pp_launch_epi<T, A_KM, B_KN>(g, epilogue, act, s)))
 }
 
-constexpr int kPersistGrid = 256;  // one workgroup per CU of an MI355X (the split-K policy below counts the same 256)
 template <typename T, bool A_KM, bool B_KN>
 static int gemm_fl_launch_epi(const GemmArgs& g, int epilogue, int act, hipStream_t s) {
   dim3 grid((unsigned)(g.tiles_m * g.tiles_n)), block(kFlThreads);
-#ifdef TAMD_DIAG  // ablation / A-B instantiations: libtamd_diag.so only, never the product library
-  const int dbg = gemm_diag_dbg();
-  if ((dbg == 32 || dbg == 128) && epilogue == TAMD_EPI_NONE) {  // the other piece placement (correct results)
-    if (dbg == 32)
-      hipLaunchKernelGGL((gemm_fl_kernel<T, A_KM, B_KN, TAMD_EPI_NONE, TAMD_ACT_NONE, 32>), grid, block, (size_t)kXSmem, s, g);
-    else
-      hipLaunchKernelGGL((gemm_fl_kernel<T, A_KM, B_KN, TAMD_EPI_NONE, TAMD_ACT_NONE, 128>), grid, block, (size_t)kXSmem, s, g);
+#ifdef TAMD_DIAG  // forced schedules: libtamd_diag.so only, never the product library; the plain epilogue only
+  if (epilogue == TAMD_EPI_NONE) {
+#define TAMD_GS(S_)                                                                                                        \
+  case S_:                                                                                                                 \
+    hipLaunchKernelGGL((gemm_fl_kernel<T, A_KM, B_KN, TAMD_EPI_NONE, TAMD_ACT_NONE, S_>), grid, block, (size_t)kXSmem, s, g); \
     return launch_status();
-  }
-  if constexpr (A_KM == B_KN) {
-    if (dbg == 32768 && (epilogue == TAMD_EPI_NONE || epilogue == TAMD_EPI_RESIDUAL)) {  // the persistent walk (prefetch under the way out), forced
-      const int tiles = g.tiles_m * g.tiles_n;
-      static const int want = [] {  // (TAMD_PERSIST_GRID: the CPU model's test walks several tiles per workgroup on a 6-tile product)
-        const char* e = getenv("TAMD_PERSIST_GRID");
-        return e ? atoi(e) : kPersistGrid;
-      }();
-      dim3 pgrid((unsigned)(tiles < want ? tiles : want));
-      if (epilogue == TAMD_EPI_NONE)
-        hipLaunchKernelGGL((gemm_fl_persist_kernel<T, A_KM, B_KN, TAMD_EPI_NONE, TAMD_ACT_NONE>), pgrid, block, (size_t)kXSmem, s, g);
-      else
-        hipLaunchKernelGGL((gemm_fl_persist_kernel<T, A_KM, B_KN, TAMD_EPI_RESIDUAL, TAMD_ACT_NONE>), pgrid, block, (size_t)kXSmem, s, g);
-      return launch_status();
+    switch (gemm_diag_dbg()) {
+      TAMD_GS(kSchedRingEarly)
+      TAMD_GS(kSchedRingLate)
+      TAMD_GS(kSchedThreeBarrier)
+      TAMD_GS(kSchedRing)
+      default: break;  // kSchedAuto: the product launch
     }
-  }
-  if (dbg == 1024 + 16384 && epilogue == TAMD_EPI_NONE) {  // the vendor table with a counted wait at the stage boundary
-    hipLaunchKernelGGL((gemm_fl_kernel<T, A_KM, B_KN, TAMD_EPI_NONE, TAMD_ACT_NONE, 1024 + 16384>), grid, block, (size_t)kXSmem, s, g);
-    return launch_status();
-  }
-  if ((dbg == 1024 + 4096 || dbg == 1024 + 8192) && epilogue == TAMD_EPI_NONE) {  // placements of the three-barrier loop: pairs / SPREAD
-    if (dbg == 1024 + 4096)
-      hipLaunchKernelGGL((gemm_fl_kernel<T, A_KM, B_KN, TAMD_EPI_NONE, TAMD_ACT_NONE, 1024 + 4096>), grid, block, (size_t)kXSmem, s, g);
-    else
-      hipLaunchKernelGGL((gemm_fl_kernel<T, A_KM, B_KN, TAMD_EPI_NONE, TAMD_ACT_NONE, 1024 + 8192>), grid, block, (size_t)kXSmem, s, g);
-    return launch_status();
-  }
-  if ((dbg == 1024 || dbg == 2048) && epilogue == TAMD_EPI_NONE) {  // round 6: the three-barrier loop / the one-barrier ring, forced
-    if (dbg == 1024)
-      hipLaunchKernelGGL((gemm_fl_kernel<T, A_KM, B_KN, TAMD_EPI_NONE, TAMD_ACT_NONE, 1024>), grid, block, (size_t)kXSmem, s, g);
-    else
-      hipLaunchKernelGGL((gemm_fl_kernel<T, A_KM, B_KN, TAMD_EPI_NONE, TAMD_ACT_NONE, 2048>), grid, block, (size_t)kXSmem, s, g);
-    return launch_status();
-  }
-  if constexpr (!A_KM) {  // round-5 placements (forward and dX layouts; correct, bit-identical results)
-    if ((dbg == 64 || dbg == 256 || dbg == 512) && epilogue == TAMD_EPI_NONE) {
-      if (dbg == 64)
-        hipLaunchKernelGGL((gemm_fl_kernel<T, A_KM, B_KN, TAMD_EPI_NONE, TAMD_ACT_NONE, 64>), grid, block, (size_t)kXSmem, s, g);
-      else if (dbg == 256)
-        hipLaunchKernelGGL((gemm_fl_kernel<T, A_KM, B_KN, TAMD_EPI_NONE, TAMD_ACT_NONE, 256>), grid, block, (size_t)kXSmem, s, g);
-      else
-        hipLaunchKernelGGL((gemm_fl_kernel<T, A_KM, B_KN, TAMD_EPI_NONE, TAMD_ACT_NONE, 512>), grid, block, (size_t)kXSmem, s, g);
-      return launch_status();
-    }
-  }
-  if (dbg && epilogue == TAMD_EPI_NONE && !A_KM && !B_KN) {
-#define TAMD_GD(N_)                                                                                             \
-  hipLaunchKernelGGL((gemm_fl_kernel<T, false, false, TAMD_EPI_NONE, TAMD_ACT_NONE, N_>), grid, block, (size_t)kXSmem, \
-                     s, g);                                                                                     \
-  return launch_status();
-    switch (dbg) {
-      case 1: TAMD_GD(1)
-      case 2: TAMD_GD(2)
-      case 4: TAMD_GD(4)
-      case 8: TAMD_GD(8)
-      case 12: TAMD_GD(12)
-      case 15: TAMD_GD(15)
-      default: break;
-    }
-#undef TAMD_GD
+#undef TAMD_GS
   }
 #endif
 #define TAMD_G(E_, A_)                                                                              \
@@ -1724,20 +1470,12 @@ static int gemm_fl_splitk_launch2(const GemmArgs& g, int epilogue, hipStream_t s
 
 template <typename T>
 static int gemm_fl_splitk_launch(const GemmArgs& g, int flags, int epilogue, hipStream_t s) {
-  const bool akm = flags & TAMD_GEMM_A_KM, bkn = flags & TAMD_GEMM_B_KN;
-  if (!akm && !bkn) return gemm_fl_splitk_launch2<T, false, false>(g, epilogue, s);
-  if (!akm && bkn) return gemm_fl_splitk_launch2<T, false, true>(g, epilogue, s);
-  if (akm && bkn) return gemm_fl_splitk_launch2<T, true, true>(g, epilogue, s);
-  return gemm_fl_splitk_launch2<T, true, false>(g, epilogue, s);
+  TAMD_DISPATCH_LAYOUT(flags, return (gemm_fl_splitk_launch2<T, A_KM, B_KN>(g, epilogue, s)))
 }
 
 template <typename T>
 static int gemm_fl_launch(const GemmArgs& g, int flags, int epilogue, int act, hipStream_t s) {
-  const bool akm = flags & TAMD_GEMM_A_KM, bkn = flags & TAMD_GEMM_B_KN;
-  if (!akm && !bkn) return gemm_fl_launch_epi<T, false, false>(g, epilogue, act, s);
-  if (!akm && bkn) return gemm_fl_launch_epi<T, false, true>(g, epilogue, act, s);
-  if (akm && bkn) return gemm_fl_launch_epi<T, true, true>(g, epilogue, act, s);
-  return gemm_fl_launch_epi<T, true, false>(g, epilogue, act, s);
+  TAMD_DISPATCH_LAYOUT(flags, return (gemm_fl_launch_epi<T, A_KM, B_KN>(g, epilogue, act, s)))
 }
 
 // the 128 x 128 kernel (row-major operands, K % 64 == 0): tiles_m / tiles_n re-counted for its tile
@@ -1759,9 +1497,11 @@ using namespace tamd;
 
 #ifdef TAMD_DIAG
 extern "C" int tamd_gemm_set_dbg(int dbg) {
+  if (!gemm_sched_known(dbg)) return TAMD_E_ARG;  // (a retired or mistyped value must not measure the product under another name)
   g_gemm_dbg = dbg;
   return TAMD_OK;
 }
+extern "C" int tamd_gemm_get_dbg(void) { return gemm_diag_dbg(); }
 static unsigned long long* g_gemm_clock = nullptr;
 extern "C" int tamd_gemm_set_clock_buffer(void* buf) {
   g_gemm_clock = reinterpret_cast<unsigned long long*>(buf);
