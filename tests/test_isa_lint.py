@@ -133,9 +133,6 @@ def test_untracked_lds_reads_are_not_touched_before_their_wait(src, flags, defin
         m = re.match(r"(_ZN4tamd\w+):", k)
         if not m or ";;#ASMSTART\n\tds_read" not in k:
             continue
-        dbg = re.search(r"ELi(\d+)ELb[01]E+vNS_11AttnBwdArgs", m.group(1))
-        if dbg and dbg.group(1) != "0":
-            continue  # ablation builds (TAMD_DKDV_DBG) drop reads / waits on purpose
         checked += 1
         body = k.split("s_endpgm")[0]
         bad += lint_kernel(m.group(1), body.splitlines())  # (a spill of a pending register is a read of it: caught)

@@ -1,5 +1,5 @@
 """Route transformers_amd.ops through libtamd_diag.so (include/tamd_diag.h): the kernel sources built with
--DTAMD_DIAG (ablation instantiations selected by TAMD_GEMM_DBG / TAMD_DKDV_DBG, phase traces) plus the probes.
+-DTAMD_DIAG (ablation instantiations selected by TAMD_GEMM_DBG, phase traces) plus the probes.
 Tools only -- the product package never loads this library."""
 import sys
 from pathlib import Path

@@ -5,7 +5,7 @@ with the srcC chains; the dropout variants 1206 -> 806 with one hash per 2 x 2 b
   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -I transformers_amd/csrc -I include \\
         -mllvm -amdgpu-mfma-vgpr-form=1 [-fno-slp-vectorize] -S --cuda-device-only \\
         -Rpass-analysis=kernel-resource-usage transformers_amd/csrc/attention_bwd_dkdv.hip -o /tmp/dkdv.s 2> /tmp/dkdv.rpass
-  python tools/isa_count.py /tmp/dkdv.s attn_bwd_dkdv_kernelINS_6bf16_tELi128ELb1ELb0ELb0ELi0ELb0 [-v] [--min-mfma 8]
+  python tools/isa_count.py /tmp/dkdv.s attn_bwd_dkdv_kernelINS_6bf16_tELi128ELb1ELb0ELb0ELb0 [-v] [--min-mfma 8]
 
 (the second argument is a substring of the kernel's mangled name; -v lists the VALU opcodes of each block; --ops prints the
 opcode sequence of each block, one per line, so that two listings can be diffed; registers, spills and occupancy are in the

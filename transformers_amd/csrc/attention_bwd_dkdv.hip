@@ -31,9 +31,11 @@
 //     branch would cut the interleave), packed-f32 VALU off (-fno-slp-vectorize: an anti-lever beside MFMAs);
 //   * the loop is unrolled over the two LDS buffers so every LDS offset is an immediate; per-lane global offsets of
 //     the LDS-DMA pieces are loop invariants; (head, tile) counters instead of divisions.
-// Measured on MI355X at the Llama-3-8B shape (tools/attn_bench.py, tools/attn_dkdv_dbg.py): whole backward 5.98 ->
-// 4.16 ms (460 -> 661 TFLOP/s); ablations of the final kernel: -0.57 ms without the softmax arithmetic, -0.44
-// without LDS fragment reads, -0.61 without MFMA: issue-slot-bound, not pipe-bound.
+// Measured on MI355X at the Llama-3-8B shape (tools/attn_bench.py): whole backward 5.98 -> 4.16 ms (460 -> 661 TFLOP/s);
+// ablations of the final kernel: -0.57 ms without the softmax arithmetic, -0.44 without LDS fragment reads, -0.61
+// without MFMA: issue-slot-bound, not pipe-bound (profiles/r01_attn_dkdv_ablation.jsonl, r03d_dkdv_ablation.txt; every
+// tile through the body with the mask test: r03l_dkdv_plain_ab.txt).  The ablation instantiations that measured this
+// are out of the source: profiles/attn_dkdv_retired_arms.patch.
 // S = Q.K^T is computed un-swapped so a lane owns a key column: the P and dS registers are directly the MFMA B
 // operands of dV^T[d][key] += dO^T[d][q].P[q][key] and dK^T[d][key] += Q^T[d][q].dS[q][key].
 #include "attention_common.h"
@@ -53,21 +55,7 @@ __device__ __forceinline__ void wait_frags(u32x4& f0, u32x4& f1, u32x4& f2, u32x
 #endif
 }
 
-// DBG (diagnostic instantiations, built only with -DTAMD_DIAG into libtamd_diag.so; TAMD_DKDV_DBG=n, wrong results): 1 no softmax arithmetic, 2 no LDS fragment reads,
-// 4 no MFMA, 8 no tile loads after the prologue, 16 no barrier; 32 (correct results) every tile through the loop body WITH the mask test
 // order-only dependency: the registers are "produced" here, after every earlier volatile asm (the waits)
-__device__ __forceinline__ void after_wait(u32x4& x0, u32x4& x1) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+v"(x0), "+v"(x1)::"memory");
-#else
-  (void)x0;
-  (void)x1;
-#endif
-}
-
-// PACKED (include/tamd.h q_start plane 1): key k is seen by queries up to k_end[k], the last token of its sequence --
-// a per-lane scalar here (a lane owns a key), so the packed mask is one more compare per element and q-tiles past
-// the block's last sequence are never visited.  A separate instantiation keeps it out of the common path.
 __device__ __forceinline__ void after_wait1(u32x4& x0) {
 #if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("" : "+v"(x0)::"memory");
@@ -85,7 +73,10 @@ __device__ __forceinline__ void after_wait_acc(f32x16& x0, f32x16& x1) {
 #endif
 }
 
-template <typename T, int D, bool CAUSAL, bool HAS_MASK, bool DROP, int DBG = 0, bool PACKED = false>
+// PACKED (include/tamd.h q_start plane 1): key k is seen by queries up to k_end[k], the last token of its sequence --
+// a per-lane scalar here (a lane owns a key), so the packed mask is one more compare per element and q-tiles past
+// the block's last sequence are never visited.  A separate instantiation keeps it out of the common path.
+template <typename T, int D, bool CAUSAL, bool HAS_MASK, bool DROP, bool PACKED>
 __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdArgs g, int nkvt) {
   const AttnArgs& a = g.f;
   constexpr int ROWB = D * 2, TILEB = kQT * ROWB, KS = D / 16, DT = D / 32, OROWB = ROWB + 16;
@@ -151,11 +142,9 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
     kf[ks] = ok ? ld16(K + (int64_t)krow * a.kss + ks * 16 + hi * 8) : u32x4{0, 0, 0, 0};
     vf[ks] = ok ? ld16(V + (int64_t)krow * a.vss + ks * 16 + hi * 8) : u32x4{0, 0, 0, 0};
   }
-  if (!(DBG & 1)) {
 #pragma unroll
-    // S leaves the MFMAs in the exp2 domain: the factor rides on K here, unless the Q tiles already carry it (q_prescaled)
-    for (int ks = 0; ks < KS; ++ks) kf[ks] = scale_frag<T, true>(kf[ks], a.scale_log2, !a.q_prescaled);
-  }
+  // S leaves the MFMAs in the exp2 domain: the factor rides on K here, unless the Q tiles already carry it (q_prescaled)
+  for (int ks = 0; ks < KS; ++ks) kf[ks] = scale_frag<T, true>(kf[ks], a.scale_log2, !a.q_prescaled);
   constexpr bool FOLD_DELTA = !DROP;  // dP's chain starts from -delta (dropout: (dP*keep - delta) is not linear in dP)
   bool key_ok = krow < a.seq_k;
   if (HAS_MASK && a.key_valid != nullptr)
@@ -291,17 +280,9 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
   }
   const unsigned stataddr[2] = {lds0 + (unsigned)hi * 16u + (unsigned)(2 * TILEB),
                                 lds0 + (unsigned)hi * 16u + (unsigned)(BUFB + 2 * TILEB)};
-  auto mm = [&](u32x4 x, u32x4 y, f32x16 c) -> f32x16 {
-    if (DBG & 4) {
-      c[0] += u32_as_f32(x[0] ^ y[0]);
-      return c;
-    }
-    return mfma32<T>(x, y, c);
-  };
   u32x4 fa[4], fb[4];  // two-group fragment ring: even groups use fa, odd groups fb (16 groups per tile: even)
   // S/dP group ga (0..NGA-1) of sub-tile `sub`: fragments Q(ks0) dO(ks0) Q(ks0+1) dO(ks0+1), ks0 = 2*ga
   auto load_rows = [&](u32x4 (&f)[4], unsigned q_off, unsigned do_off, int sub, int ga) {
-    if (DBG & 2) return;
     const int si = sub * 32 * ROWB;
     f[0] = lds_read16_abs(rowaddr[2 * ga], (int)q_off + si);
     f[1] = lds_read16_abs(rowaddr[2 * ga], (int)do_off + si);
@@ -317,7 +298,6 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
     return u32x4{lo[0], lo[1], h2[0], h2[1]};
   };
   auto load_tr = [&](u32x4 (&f)[4], unsigned q_off, unsigned do_off, int dtp, int j) {
-    if (DBG & 2) return;
     f[0] = tr_frag(do_off, 2 * dtp, j);
     f[1] = tr_frag(q_off, 2 * dtp, j);
     f[2] = tr_frag(do_off, 2 * dtp + 1, j);
@@ -329,11 +309,9 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
   auto load_stats = [&](f32x16& s_, f32x16& dp_, int buf, int sub) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      u32x4 l4 = {0u, 0u, 0u, 0u}, d4 = {0u, 0u, 0u, 0u};
-      if (!(DBG & 1)) {
-        l4 = lds_read16_abs(stataddr[buf], (sub * 32 + 8 * j) * 4);
-        if (FOLD_DELTA) d4 = lds_read16_abs(stataddr[buf], (sub * 32 + 8 * j) * 4 + kQT * 4);
-      }
+      const u32x4 l4 = lds_read16_abs(stataddr[buf], (sub * 32 + 8 * j) * 4);
+      u32x4 d4 = {0u, 0u, 0u, 0u};
+      if (FOLD_DELTA) d4 = lds_read16_abs(stataddr[buf], (sub * 32 + 8 * j) * 4 + kQT * 4);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         s_[4 * j + e] = u32_as_f32(l4[e]);
@@ -341,7 +319,7 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
       }
     }
   };
-  constexpr int NSTAT = (DBG & 1) ? 0 : (FOLD_DELTA ? 8 : 4);  // LDS reads of one load_stats
+  constexpr int NSTAT = FOLD_DELTA ? 8 : 4;  // LDS reads of one load_stats
 
   if (niter > 0) issue(0, 0);
   wait_vmcnt0();
@@ -362,7 +340,6 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
   // reads): groups 0 .. 2*NGA-1 are S / dP of the two sub-tiles (Q(ks0) dO(ks0) Q(ks0+1) dO(ks0+1)), the others dV / dK
   // (dO^T(dt0,j) Q^T(dt0,j) dO^T(dt1,j) Q^T(dt1,j))
   auto req = [&](int buf, int m, int j) {
-    if (DBG & 2) return;
     const unsigned q_off = (unsigned)buf * BUFB, do_off = q_off + TILEB;
     u32x4(&f)[4] = (m & 1) ? fb : fa;
     if (m < 2 * NGA) {
@@ -387,6 +364,14 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
   }
   const int niter2 = (niter + 1) & ~1;  // even: an odd count gets one all-zero padding tile
   int cmp_h = 0, cmp_qt = nqt64 - 1;    // (head, q-tile) of the tile being computed
+  // The hand-off of both loop bodies, placed before the last MFMA group of a tile: by then every fragment of this tile is in registers, so the
+  // buffer can take tile it+2 at once; tile it+1 (requested during this tile) must have landed
+  auto hand_off = [&]() {
+    wait_vmcnt0();
+    wait_lgkmcnt0();
+    raw_barrier();
+    sched_fence();
+  };
   // Two copies of the loop body.  PLAIN: the tile needs no mask for any key of this wave (every key of the wave valid,
   // and, causal, the tile's first query row sees the wave's last key): no mask test -- 2 VALU per element, 64 of the
   // ~420 instructions beside the 64 MFMAs of a tile, on a loop that is bound by instruction issue (4-5 instructions hide
@@ -406,22 +391,13 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
       cmp_h = 0;
       --cmp_qt;
     }
-    // hand-off, placed before the last MFMA group of the tile: by then every fragment of this tile is in
-    // registers, so the buffer can take tile it+2 at once; tile it+1 (requested one tile ago) must have landed
-    auto hand_off = [&]() {
-      wait_vmcnt0();
-      wait_lgkmcnt0();
-      if (!(DBG & 16)) raw_barrier();
-      sched_fence();
-    };
     // tile it+1 goes out behind the first NPIECE MFMA groups of this tile (the last tile of the loop requests nothing)
     // (no branch: behind the last tile of the loop issue_begin finds no rows, the pieces fetch nothing and zeros land in the
     // buffer nobody reads any more)
-    if (!(DBG & 8)) issue_begin(it + 1);
+    issue_begin(it + 1);
     // ... strictly BEHIND the group's MFMAs (the scheduler otherwise puts the piece behind the first one: one queued MFMA to
     // cover a 60-185 cycle issue instead of four)
     auto feed_piece = [&](int gidx) {  // one piece behind each of the groups 0 .. NPIECE-1
-      if (DBG & 8) return;
       sched_fence();
       if (gidx < NPIECE) issue_piece(cur ^ 1, gidx);
     };
@@ -438,21 +414,13 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
     // P and dS, rounded and packed at once into B operand sub*2 + (qd>>1), dwords (qd&1)*2 .. +1
     // lse / delta of 4 consecutive query rows of chunk qd (16 bytes each; lane part of the address = 16*hi)
     // (only the dropout variants still read -delta beside the arithmetic; NSR = reads per chunk)
-    constexpr int NSR = ((DBG & 1) || FOLD_DELTA) ? 0 : 1;
+    constexpr int NSR = FOLD_DELTA ? 0 : 1;
     auto stat_reads = [&](int sub, int qd, u32x4& d4) {
       if (NSR == 0) return;
       const int imm = (sub * 32 + 8 * qd) * 4;  // (st_off of the second buffer does not fit the 16-bit offset field)
       d4 = lds_read16_abs(stataddr[cur], imm + kQT * 4);
     };
     auto softmax_chunk = [&](int sub, int qd, const u32x4& d4) {
-      if (DBG & 1) {
-        const int op = sub * 2 + (qd >> 1), w = (qd & 1) * 2;
-        pf[op][w] = f32_as_u32(s[sub][qd * 4]);
-        pf[op][w + 1] = f32_as_u32(s[sub][qd * 4 + 1]);
-        dsf[op][w] = f32_as_u32(dp[sub][qd * 4]);
-        dsf[op][w + 1] = f32_as_u32(dp[sub][qd * 4 + 1]);
-        return;
-      }
       float p[4], ds[4];
       const int ql = sub * 32 + 8 * qd + 4 * hi;  // 4 consecutive query rows (r&3)
       bool keep4[4] = {true, true, true, true};
@@ -550,10 +518,10 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
           for (int c = 0; c < NCH_A; ++c) after_wait1(d4[c]);
         }
         sched_fence();
-        s[sub] = mm(fc[0], kf[2 * ga], s[sub]);
-        dp[sub] = mm(fc[1], vf[2 * ga], dp[sub]);
-        s[sub] = mm(fc[2], kf[2 * ga + 1], s[sub]);
-        dp[sub] = mm(fc[3], vf[2 * ga + 1], dp[sub]);
+        s[sub] = mfma32<T>(fc[0], kf[2 * ga], s[sub]);
+        dp[sub] = mfma32<T>(fc[1], vf[2 * ga], dp[sub]);
+        s[sub] = mfma32<T>(fc[2], kf[2 * ga + 1], s[sub]);
+        dp[sub] = mfma32<T>(fc[3], vf[2 * ga + 1], dp[sub]);
         if (sub == 1) {  // softmax backward of sub-tile 0 in the shadow of these MFMAs (NGA = 2: two chunks)
 #pragma unroll
           for (int c = 0; c < NCH_A; ++c) softmax_chunk(0, ga * NCH_A + c, d4[c]);
@@ -597,10 +565,10 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
           for (int c = 0; c < NCH_C; ++c) after_wait1(d4[c]);
         }
         sched_fence();
-        dvacc[2 * dtp] = mm(fc[0], pf[j], dvacc[2 * dtp]);
-        dkacc[2 * dtp] = mm(fc[1], dsf[j], dkacc[2 * dtp]);
-        dvacc[2 * dtp + 1] = mm(fc[2], pf[j], dvacc[2 * dtp + 1]);
-        dkacc[2 * dtp + 1] = mm(fc[3], dsf[j], dkacc[2 * dtp + 1]);
+        dvacc[2 * dtp] = mfma32<T>(fc[0], pf[j], dvacc[2 * dtp]);
+        dkacc[2 * dtp] = mfma32<T>(fc[1], dsf[j], dkacc[2 * dtp]);
+        dvacc[2 * dtp + 1] = mfma32<T>(fc[2], pf[j], dvacc[2 * dtp + 1]);
+        dkacc[2 * dtp + 1] = mfma32<T>(fc[3], dsf[j], dkacc[2 * dtp + 1]);
         if (half == 0) {  // softmax backward of sub-tile 1 in the shadow of these MFMAs
 #pragma unroll
           for (int c = 0; c < NCH_C; ++c) softmax_chunk(1, gc * NCH_C + c, d4[c]);
@@ -636,7 +604,7 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
       cmp_h = 0;
       --cmp_qt;
     }
-    if (!(DBG & 8)) issue_begin(it + 1);
+    issue_begin(it + 1);
     const int mask_lim = key_ok ? (CAUSAL ? krow - (qt0 + off) : -0x40000000) : 0x40000000;
     const int mask_hi = kend - qt0;  // PACKED: last local query row of this tile that belongs to the key's sequence
     sched_fence();
@@ -650,16 +618,6 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
     // slice k of the softmax backward of chunk qd of sub-tile sub (4 consecutive query rows: C-layout registers qd*4 .. +3):
     // three instructions per slice for a tile that needs no mask
     auto slice = [&](int sub, int qd, int c, int k) {
-      if (DBG & 1) {
-        if (k == 3) {
-          const int op = sub * 2 + (qd >> 1), w = (qd & 1) * 2;
-          pf[op][w] = f32_as_u32(s[sub][qd * 4]);
-          pf[op][w + 1] = f32_as_u32(s[sub][qd * 4 + 1]);
-          dsf[op][w] = f32_as_u32(dp[sub][qd * 4]);
-          dsf[op][w + 1] = f32_as_u32(dp[sub][qd * 4 + 1]);
-        }
-        return;
-      }
       const int ql = sub * 32 + 8 * qd + 4 * hi;
       auto ex = [&](int e) {
         float x = s[sub][qd * 4 + e];
@@ -690,7 +648,7 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
       }
     };
     constexpr int RA = 1, RC = 2;  // LDS reads per fragment: one b128 row read, two transposing reads
-    auto nreads = [&](int m) -> int { return (DBG & 2) ? 0 : (((m % G) < 2 * NGA) ? RA : RC); };
+    auto nreads = [&](int m) -> int { return ((m % G) < 2 * NGA) ? RA : RC; };
 #pragma unroll
     for (int m = 0; m < G; ++m) {
       u32x4(&fc)[4] = (m & 1) ? fb : fa;
@@ -700,13 +658,10 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
       const int dtp = gc >> 1, jc = half * 2 + (gc & 1);
       // ---- this group's fragments have landed
       if (m == G - 1) {  // hand-off: every fragment of this tile is in registers; tile it+1 (requested during this tile) has landed
-        wait_vmcnt0();
-        wait_lgkmcnt0();
-        if (!(DBG & 16)) raw_barrier();
-        sched_fence();
+        hand_off();
         wait_frags<15>(fc[0], fc[1], fc[2], fc[3]);  // dependency only
       } else {
-        const int behind = 3 * nreads(m + 1) + ((m == 1 && !(DBG & 1)) ? 6 : 0);  // (group 0's gaps 1 .. 3 also carry statistics reads)
+        const int behind = 3 * nreads(m + 1) + (m == 1 ? 6 : 0);  // (group 0's gaps 1 .. 3 also carry statistics reads)
         if (behind >= 9)
           wait_frags<9>(fc[0], fc[1], fc[2], fc[3]);
         else if (behind >= 6)
@@ -724,34 +679,27 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
         // ---- MFMA k of the group
         if (aph) {
           if (k & 1)
-            dp[sub] = mm(fc[k], vf[2 * ga + (k >> 1)], dp[sub]);
+            dp[sub] = mfma32<T>(fc[k], vf[2 * ga + (k >> 1)], dp[sub]);
           else
-            s[sub] = mm(fc[k], kf[2 * ga + (k >> 1)], s[sub]);
+            s[sub] = mfma32<T>(fc[k], kf[2 * ga + (k >> 1)], s[sub]);
         } else {
           if (k & 1)
-            dkacc[2 * dtp + (k >> 1)] = mm(fc[k], dsf[jc], dkacc[2 * dtp + (k >> 1)]);
+            dkacc[2 * dtp + (k >> 1)] = mfma32<T>(fc[k], dsf[jc], dkacc[2 * dtp + (k >> 1)]);
           else
-            dvacc[2 * dtp + (k >> 1)] = mm(fc[k], pf[jc], dvacc[2 * dtp + (k >> 1)]);
+            dvacc[2 * dtp + (k >> 1)] = mfma32<T>(fc[k], pf[jc], dvacc[2 * dtp + (k >> 1)]);
         }
         // ---- its gap
         // statistics that start sub-tile 1's chains: two reads in each of the gaps (0, 1), (0, 2), (0, 3), (1, 0), BEFORE the
         // gap's fragment request (the wait counts above rely on that order)
         {
           const int jst = (m == 0) ? k - 1 : (m == 1 && k == 0 ? 3 : -1);
-          if (jst >= 0 && !(DBG & 1)) {
+          if (jst >= 0) {
             const u32x4 l4 = lds_read16_abs(stataddr[cur], (32 + 8 * jst) * 4);
             const u32x4 d4 = lds_read16_abs(stataddr[cur], (32 + 8 * jst) * 4 + kQT * 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               s[1][4 * jst + e] = u32_as_f32(l4[e]);
               dp[1][4 * jst + e] = u32_as_f32(d4[e]);
-            }
-          }
-          if (m == 0 && k == 0 && (DBG & 1)) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              s[1][r] = 0.f;
-              dp[1][r] = 0.f;
             }
           }
         }
@@ -782,7 +730,7 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
         }
         // a piece of the next tile in the first gap of the groups 0 .. NPIECE-1 (measured level with / 0.4-0.9 % ahead of "behind
         // the group's last MFMA", profiles/r05h_, r05i_attn_variants_ab.jsonl)
-        if (k == 0 && m < NPIECE && !(DBG & 8)) issue_piece(cur ^ 1, m);
+        if (k == 0 && m < NPIECE) issue_piece(cur ^ 1, m);
         sched_fence();
       }
     }
@@ -790,7 +738,7 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
   };
   int it_plain = 0;  // (even) leading tiles of this wave that take the body without the mask test
   int it_first = 0;  // PACKED: (even) tiles in front of them whose last rows lie behind the end of a key's sequence / window
-  if (!(DBG & 32) && ballot64(key_ok) == ~0ull) {
+  if (ballot64(key_ok) == ~0ull) {
     int n = niter2;
     if (CAUSAL) {
       const int need = kw0 + 31 - off;                       // first query row that sees the wave's last key
@@ -813,32 +761,30 @@ __global__ __launch_bounds__(kAttnThreads, 1) void attn_bwd_dkdv_kernel(AttnBwdA
       it_first = it_first < it_plain ? it_first : it_plain;
     }
   }
+  // pair(plain_c, it0): one pair of tiles through the body of this variant, without (PLAIN) or with the mask test.  (A name for
+  // the body itself: a forwarding lambda that called it changed the registers of every variant without dropout, and a helper
+  // that took both bodies the loop prologue of the dropout ones -- profiles/attn_dkdv_retire_isa.md.)
+  auto& pair = [&]() -> auto& {
+    if constexpr (FINE)
+      return tile_pair_fine;
+    else
+      return tile_pair;
+  }();
+  constexpr bool TWO = FINE || !(DROP && D > 64);  // (two bodies of the dropout variant at head_dim 128 do not fit the registers)
   int it0 = 0;
   if constexpr (PACKED) {
     // one loop, a wave-uniform choice of the body per tile pair (two copies of the body, as in the other variants)
-    constexpr bool TWO = FINE || !(DROP && D > 64);  // (two bodies of the dropout variant at head_dim 128 do not fit the registers)
     for (; it0 < niter2; it0 += 2) {
-      const bool plain = TWO && it0 >= it_first && it0 < it_plain;
-      if constexpr (FINE) {
-        if (plain)
-          tile_pair_fine(IntC<1>{}, it0);
-        else
-          tile_pair_fine(IntC<0>{}, it0);
-      } else {
-        if (plain)
-          tile_pair(IntC<(TWO ? 1 : 0)>{}, it0);
-        else
-          tile_pair(IntC<0>{}, it0);
-      }
+      if (TWO && it0 >= it_first && it0 < it_plain)
+        pair(IntC<(TWO ? 1 : 0)>{}, it0);
+      else
+        pair(IntC<0>{}, it0);
     }
-  } else if constexpr (FINE) {
-    for (; it0 < it_plain; it0 += 2) tile_pair_fine(IntC<1>{}, it0);
-    for (; it0 < niter2; it0 += 2) tile_pair_fine(IntC<0>{}, it0);
   } else {
-    if (!(DROP && D > 64)) {  // (two bodies of the dropout variant at head_dim 128 do not fit the registers)
-      for (; it0 < it_plain; it0 += 2) tile_pair(IntC<1>{}, it0);
+    if (TWO) {
+      for (; it0 < it_plain; it0 += 2) pair(IntC<1>{}, it0);
     }
-    for (; it0 < niter2; it0 += 2) tile_pair(IntC<0>{}, it0);
+    for (; it0 < niter2; it0 += 2) pair(IntC<0>{}, it0);
   }
   // the last hand-off left nothing in flight; every wave is past its LDS reads only after a barrier
   wait_vmcnt0();
@@ -863,43 +809,27 @@ static int dkdv_launch(const AttnBwdArgs& g, bool causal, hipStream_t s) {
   const int nkvt = (int)ceil_div(a.seq_k, kKVB);
   const size_t smem = (size_t)2 * (2 * kQT * D * 2 + 2 * kQT * 4);
   dim3 grid((unsigned)(nkvt * a.heads_kv * a.batch)), block(kAttnThreads);
-#define TAMD_KV(C_, M_, D_) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, D, C_, M_, D_>), grid, block, smem, s, g, nkvt)
+#define TAMD_KV(C_, M_, D_, P_) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, D, C_, M_, D_, P_>), grid, block, smem, s, g, nkvt)
   if (a.q_start != nullptr) {  // packed sequences (causal only, checked by the caller)
     if (drop)
-      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, D, true, true, true, 0, true>), grid, block, smem, s, g, nkvt);
+      TAMD_KV(true, true, true, true);
     else
-      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, D, true, true, false, 0, true>), grid, block, smem, s, g, nkvt);
-    return launch_status();
-  }
-  if (drop) {  // the dropout variants always carry the padding-mask code
+      TAMD_KV(true, true, false, true);
+  } else if (drop) {  // the dropout variants always carry the padding-mask code
     if (causal)
-      TAMD_KV(true, true, true);
+      TAMD_KV(true, true, true, false);
     else
-      TAMD_KV(false, true, true);
+      TAMD_KV(false, true, true, false);
   } else if (causal) {
-    if (mask) {
-      TAMD_KV(true, true, false);
-      return launch_status();
-    }
-#ifdef TAMD_DIAG  // ablation instantiations (wrong results by design): libtamd_diag.so only
-    static const int dbg = [] {
-      const char* e = getenv("TAMD_DKDV_DBG");
-      return e ? atoi(e) : 0;
-    }();
-#define TAMD_KVD(N_)                                                                                          \
-  if (dbg == N_) {                                                                                            \
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, D, true, false, false, N_>), grid, block, smem, s, g, nkvt);  \
-    return launch_status();                                                                                   \
-  }
-    TAMD_KVD(1) TAMD_KVD(2) TAMD_KVD(4) TAMD_KVD(8) TAMD_KVD(16) TAMD_KVD(3) TAMD_KVD(7) TAMD_KVD(6) TAMD_KVD(32)
-#undef TAMD_KVD
-#endif
-    TAMD_KV(true, false, false);
+    if (mask)
+      TAMD_KV(true, true, false, false);
+    else
+      TAMD_KV(true, false, false, false);
   } else {
     if (mask)
-      TAMD_KV(false, true, false);
+      TAMD_KV(false, true, false, false);
     else
-      TAMD_KV(false, false, false);
+      TAMD_KV(false, false, false, false);
   }
 #undef TAMD_KV
   return launch_status();
