@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define TAMD_ABI_VERSION 12
+#define TAMD_ABI_VERSION 13
 
 typedef void* tamd_stream_t; /* hipStream_t */
 
@@ -370,12 +370,25 @@ struct tamd_attn_params {
    * written by a captured RNG kernel (torch: `torch.empty(1, dtype=int64, device=...).random_()`, whose philox offset
    * advances per replay).  The mask of seed value s is the same whichever way s arrives. */
   const uint64_t* dropout_seed_dev;
+  /* ABI 13.  tamd_attn_decode only: the number of keys IN USE per batch row, int32 [batch] in DEVICE memory (the
+   * `cache_seqlens` of a pre-allocated KV cache: StaticCache, cache_utils.py), or NULL = seq_k for every row.  k / v / key_valid
+   * keep describing the whole allocation of seq_k slots; batch row b is computed exactly as if k and v had been sliced to
+   *   len_b = min(max(seq_k_dev[b], 0), seq_k)
+   * rows: the causal diagonal is bottom-right aligned to len_b (key k visible to query s iff k <= s + len_b - seq_q), keys
+   * >= len_b are invisible, key tiles at or behind len_b are neither loaded nor visited and slots >= len_b of the ragged
+   * tile never reach the arithmetic -- whatever an unused slot holds (NaN included) has no effect, and the time follows
+   * the keys in use.  key_valid keeps its [batch, seq_k] row stride.  A row without a visible key (len_b = 0, or a causal
+   * row above the diagonal) gives O = 0, lse = +inf.  The schedule and the workspace remain functions of seq_k alone (no
+   * device data on the host).  Not with q_start or dropout; tamd_attn_fwd / tamd_attn_bwd return TAMD_E_ARG when it is
+   * set (inference only). */
+  const int32_t* seq_k_dev;
 };
 int tamd_attn_fwd(const struct tamd_attn_params* p, tamd_stream_t stream);
 
 /* ABI 8.  The same attention for DECODE shapes -- a few query rows (one new token per sequence, or a short speculative /
  * chunked block) over a long key range: the KV cache of `generate` (cache_utils.py:1730, :1822; modeling_llama.py:243-281).
- * Same parameter block and result as tamd_attn_fwd (dropout_p must be 0, q_start NULL), different schedule: with one query row
+ * Same parameter block and result as tamd_attn_fwd (dropout_p must be 0, q_start NULL; ABI 13: seq_k_dev is honoured here, for
+ * any seq_q), different schedule: with one query row
  * and grouped-query attention the query heads of a KV head share one pass over its keys, and the key range is split over
  * enough workgroups to fill the GPU (split-KV; fp32 partial rows in `workspace`, merged by a second kernel).
  * workspace: tamd_attn_decode_workspace_bytes(p) bytes, 16-byte aligned. */

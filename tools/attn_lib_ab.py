@@ -21,7 +21,7 @@ from transformers_amd._cabi import AttnBwdParams, AttnParams, TamdLib, TAMD_BF16
 # parameter blocks as an ABI-6 build lays them out (tamd_attn_params grew by q_prescaled in ABI 7, which moves every field
 # of tamd_attn_bwd_params behind the embedded block)
 class AttnParamsV6(ctypes.Structure):
-    _fields_ = [f for f in AttnParams._fields_ if f[0] not in ("q_prescaled", "dropout_seed_dev")]
+    _fields_ = [f for f in AttnParams._fields_ if f[0] not in ("q_prescaled", "dropout_seed_dev", "seq_k_dev")]
 
 
 class AttnBwdParamsV6(ctypes.Structure):
@@ -83,7 +83,7 @@ def reference(q, k, v, do, scale, causal, nb=1, nh=2):
 def main():
     base = Path(sys.argv[1]) if len(sys.argv) > 1 else ROOT / "tools" / "ab" / "libtamd_base.so"
     new = Path(sys.argv[2]) if len(sys.argv) > 2 else ROOT / "transformers_amd" / "libtamd.so"
-    libs = {"base": TamdLib(base, accept_abi=(6, 7, 8, 9)), "new": TamdLib(new)}  # (the struct grew at its end: ABI 6 reads a prefix)
+    libs = {"base": TamdLib(base, accept_abi=(6, 7, 8, 9, 10, 11, 12)), "new": TamdLib(new)}  # (the struct grew at its end: an earlier ABI reads a prefix)
     for extra in sys.argv[3:]:  # further builds of the current ABI (tools/build_variant.py), tagged by their file name
         libs[Path(extra).stem.replace("libtamd_", "")] = TamdLib(Path(extra))
     if os.environ.get("AB_LIBS"):  # e.g. AB_LIBS=new under rocprofv3: kernel names of one build only

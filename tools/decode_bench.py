@@ -1,7 +1,10 @@
 """Decode attention (tamd_attn_decode: split-KV over a KV cache) on one MI355X.
   kernels   per shape: the split-KV schedule vs the training kernel (tamd_attn_fwd on the same call) vs torch SDPA -- us per call
             and the K+V bytes of the cache / time (the HBM roofline of a decode step's attention: every cached key and value
-            is read once)
+            is read once); then a decode step over a PRE-ALLOCATED cache of 8192 slots with 512 and with 8192 in use, three
+            forms of the same step: (a) a validity plane over the whole cache, (b) the key counts in device memory
+            (tamd_attn_params.seq_k_dev), (c) K / V sliced to the slots in use (what a dynamic cache costs: the floor)
+            (`kernels-static`: these rows alone)
   generate  `model.generate` of a Llama-3-8B-shaped model (DECODE_BENCH_LAYERS layers, default 8, random init) after a 4096-token
             prompt: new tokens / s with attn_implementation="tamd" (and, in child processes, with the M = batch projections kept
             on the MFMA tiles, TAMD_GEMM=x, and with the training attention kernel, TAMD_DECODE_KERNEL=0) and "sdpa"
@@ -75,6 +78,75 @@ def kernels():
                           "err_vs_fp32": None if ref is None else round(((o_dec.float() - ref).norm() / ref.norm()).item(), 5)}), flush=True)
 
 
+def _plan(b, hq, hkv, sk):
+    """(pieces, key tiles per piece) of tamd_attn_decode's split-KV plan for one query row per sequence (csrc/attention.hip
+    decode_plan: the query heads of a KV head are the rows of one tile, so a (sequence, KV head) pair is cut into `pieces`
+    workgroups); checked against the workspace size by the caller."""
+    nkt = -(-sk // 64)
+    base = hkv * b if hq != hkv else hq * b
+    splits = max(1, min(-(-768 // base), nkt, 256))
+    tps = -(-nkt // splits)
+    return -(-nkt // tps), tps
+
+
+def static_cache_rows():
+    """A decode step's attention over a pre-allocated cache, Llama-3-8B heads: us per call of the three forms, measured in one
+    process and interleaved (a b c, a b c, ...); `wg_with_work` / `wg` = workgroups of the split-KV kernel that visit at least
+    one key tile / that are launched (the plan follows the allocation, so at a short count only the first pieces work)."""
+    be = ops.backend()
+    lib = be.lib
+    hq, hkv, d, alloc = 32, 8, 128, 8192
+    scale = d ** -0.5
+    for b in (1, 8):
+        torch.manual_seed(0)
+        q = torch.randn(b, 1, hq, d, device=dev).bfloat16()
+        kc = torch.randn(b, alloc, hkv, d, device=dev).bfloat16()
+        vc = torch.randn(b, alloc, hkv, d, device=dev).bfloat16()
+        stream = ctypes.c_void_p(be.stream(q))
+        for used in (512, 8192):
+            plane = (torch.arange(alloc, device=dev)[None] < used).expand(b, -1).to(torch.uint8).contiguous()
+            counts = torch.full((b,), used, dtype=torch.int32, device=dev)
+            forms = {}
+            for tag, k, v, kvp, cnt in (("plane", kc, vc, plane, None), ("seq_k_dev", kc, vc, None, counts),
+                                        ("sliced", kc[:, :used], vc[:, :used], None, None)):
+                o = torch.empty_like(q)
+                ap = _cabi.AttnParams()
+                ap.q, ap.k, ap.v, ap.o, ap.lse, ap.q_start = q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), None, None
+                ap.key_valid = None if kvp is None else kvp.data_ptr()
+                ap.seq_k_dev = None if cnt is None else cnt.data_ptr()
+                ap.batch, ap.seq_q, ap.heads_q, ap.head_dim, ap.seq_k, ap.heads_kv = b, 1, hq, d, k.shape[1], hkv
+                for nm, t in (("q", q), ("k", k), ("v", v), ("o", o)):
+                    setattr(ap, f"{nm}_stride_b", t.stride(0))
+                    setattr(ap, f"{nm}_stride_s", t.stride(1))
+                    setattr(ap, f"{nm}_stride_h", t.stride(2))
+                ap.scale, ap.causal, ap.dtype, ap.dropout_p, ap.dropout_seed, ap.q_prescaled = scale, 1, _cabi.TAMD_BF16, 0.0, 0, 0
+                nbytes = lib.tamd_attn_decode_workspace_bytes(ctypes.byref(ap))
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                pieces, tps = _plan(b, hq, hkv, k.shape[1])
+                assert nbytes == pieces * b * hq * (d + 1) * 4, (nbytes, pieces)
+                working = min(pieces, -(-(-(-used // 64)) // tps))  # pieces whose first tile lies below the count
+                fn = (lambda ap=ap, ws=ws, nbytes=nbytes: lib.check(
+                    lib.tamd_attn_decode(ctypes.byref(ap), ws.data_ptr(), nbytes, stream), "decode"))
+                forms[tag] = (fn, o, pieces * b * hkv, working * b * hkv, (ap, ws, k, v, kvp, cnt))
+            times = {t: [] for t in forms}
+            for _ in range(5):  # interleaved rounds: a b c, a b c, ...
+                for tag, (fn, *_r) in forms.items():
+                    times[tag].append(timeit(fn, iters=2000, warm=20))
+            ref = torch.nn.functional.scaled_dot_product_attention(
+                q.transpose(1, 2).float(), kc[:, :used].transpose(1, 2).float(), vc[:, :used].transpose(1, 2).float(),
+                enable_gqa=True).transpose(1, 2)
+            kv_bytes = 2.0 * b * used * hkv * d * 2
+            row = {"bench": "kernels-static", "shape": f"llama3-8b b{b}, cache {alloc}, {used} in use", "b": b, "alloc": alloc,
+                   "used": used, "hq": hq, "hkv": hkv, "d": d}
+            for tag, (fn, o, wg, wg_work, _keep) in forms.items():
+                ts = sorted(times[tag])
+                row[tag] = {"us": round(ts[len(ts) // 2], 1), "us_all": [round(x, 1) for x in times[tag]],
+                            "GBps_of_used_kv": round(kv_bytes / ts[len(ts) // 2] / 1e3), "wg": wg, "wg_with_work": wg_work,
+                            "err_vs_fp32": round(((o.float() - ref).norm() / ref.norm()).item(), 5)}
+            row["seq_k_dev_same_bits_as_plane"] = bool(torch.equal(forms["seq_k_dev"][1], forms["plane"][1]))
+            print(json.dumps(row), flush=True)
+
+
 def generate(arm):
     from transformers import LlamaConfig, LlamaForCausalLM
 
@@ -116,6 +188,8 @@ if __name__ == "__main__":
     which = sys.argv[1:] or ["kernels", "generate"]
     if "kernels" in which:
         kernels()
+    if "kernels" in which or "kernels-static" in which:
+        static_cache_rows()
     if "generate" in which:
         arm = os.environ.get("DECODE_BENCH_ARM")
         if arm:

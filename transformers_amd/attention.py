@@ -23,14 +23,27 @@ ATTN_KEY = "tamd"
 
 
 class TamdMask:
-    """What `tamd_mask` hands to the attention function for packed sequences: the 2-D key-validity mask (or None) plus
-    `q_start` (int32 [2, B, S]: first token of every query's sequence, last token of every key's sequence).  The
-    decoder layers pass it along untouched as `attention_mask`."""
+    """What `tamd_mask` hands to the attention function when a 2-D mask does not say it all: the 2-D key-validity mask (or
+    None) plus, for packed sequences, `q_start` (int32 [2, B, S]: first token of every query's sequence, last token of every
+    key's sequence) or, for a decode step over a pre-allocated cache, `kv_len` (int32 [B] on the device: the key slots in use,
+    `tamd_attn_params.seq_k_dev` -- the key-validity mask then covers the whole allocation).  The decoder layers pass it
+    along untouched as `attention_mask`."""
 
-    __slots__ = ("key_valid", "q_start")
+    __slots__ = ("key_valid", "q_start", "kv_len")
 
-    def __init__(self, key_valid, q_start):
-        self.key_valid, self.q_start = key_valid, q_start
+    def __init__(self, key_valid, q_start, kv_len=None):
+        self.key_valid, self.q_start, self.kv_len = key_valid, q_start, kv_len
+
+    # `generate` with a pre-allocated cache prepares the step's mask BEFORE the forward (generation/utils.py
+    # prepare_inputs_for_generation -> create_masks_for_generate), and the forward's own create_causal_mask then receives that
+    # object as `attention_mask`: masking_utils._preprocess_mask_arguments asks it for `.ndim` and moves it with `.to(...)`
+    # before it reaches `tamd_mask` again, which hands it back as it is.  It stands for a 2-D mask.
+    ndim = 2
+
+    def to(self, device=None, dtype=None, **_kw):
+        move = (lambda t: t if t is None else t.to(device=device))
+        kv = self.key_valid if self.key_valid is None else self.key_valid.to(device=device, dtype=dtype)
+        return TamdMask(kv, move(self.q_start), move(self.kv_len))
 
 
 def _mask_kv_len(attention_mask) -> Optional[int]:
@@ -76,6 +89,8 @@ def tamd_mask(batch_size, q_length, kv_length, q_offset=0, kv_offset=0, mask_fun
     other mask function (bidirectional windows, blockwise, user overlays) is refused instead of being silently ignored."""
     from transformers import masking_utils as mu
 
+    if isinstance(attention_mask, TamdMask):  # this step's mask, prepared before the forward (see TamdMask): nothing to add
+        return attention_mask
     # 2-D padding mask over the kv window [kv_offset, kv_offset + kv_length), padded with zeros on the right when it
     # is shorter than the window (pre-allocated caches), as prepare_padding_mask does (masking_utils.py:205-215)
     padding = attention_mask
@@ -100,7 +115,17 @@ def tamd_mask(batch_size, q_length, kv_length, q_offset=0, kv_offset=0, mask_fun
         if kv_offset != 0:
             raise TamdError("attn_implementation='tamd' does not implement sliding-window KV caches (kv_offset != 0); "
                             "use attn_implementation='sdpa' or 'eager'")
-        if q_length == 1:  # decode: one query sees keys 0 .. q_offset; stays on the device (q_offset may be a tensor)
+        if q_length == 1 and mask_function in (None, mu.causal_mask_function):
+            # decode: one query sees keys 0 .. q_offset.  The count travels as an int32 [B] tensor on the device (q_offset may be
+            # a tensor: no host synchronisation) and the kernel reads it there: key tiles behind it are neither loaded nor
+            # visited, whatever the unused slots hold.  The padding mask keeps the allocation's length (zero tail).
+            dev = padding.device if padding is not None else kwargs.get("device")
+            if torch.is_tensor(q_offset):
+                count = (q_offset.reshape(-1)[:1].to(device=dev, dtype=torch.int32) + 1).expand(batch_size).contiguous()
+            else:
+                count = torch.full((batch_size,), int(q_offset) + 1, dtype=torch.int32, device=dev)
+            return TamdMask(padding, None, count)
+        if q_length == 1:  # ... under an overlay: the dense plane of the slots in use (the overlays below refuse a cache)
             dev = padding.device if padding is not None else kwargs.get("device")
             used = torch.arange(kv_length, device=dev)[None] <= torch.as_tensor(q_offset, device=dev)
             padding = used.expand(batch_size, -1) if padding is None else (padding.to(torch.bool) & used)
@@ -158,14 +183,28 @@ def _overlay_kind(leaf) -> Optional[str]:
             "chunked_overlay": "chunked"}.get(factory)
 
 
-def split_mask(attention_mask, batch: int, kv_len: int):
-    """(key_valid [B, kv_len] bool or None, q_start int32 [2, B, S] or None) from whatever reached the attention layer."""
+def split_mask_kv(attention_mask, batch: int, kv_len: int):
+    """(key_valid [B, kv_len] bool or None, q_start int32 [2, B, S] or None, key counts int32 [B] or None) from whatever
+    reached the attention function."""
     if isinstance(attention_mask, TamdMask):
         kv = None if attention_mask.key_valid is None else _key_valid_from_mask(attention_mask.key_valid, batch, kv_len)
-        return kv, attention_mask.q_start
+        return kv, attention_mask.q_start, attention_mask.kv_len
     if attention_mask is None:
-        return None, None
-    return _key_valid_from_mask(attention_mask, batch, kv_len), None
+        return None, None, None
+    return _key_valid_from_mask(attention_mask, batch, kv_len), None, None
+
+
+def _refuse_kv_len(attention_mask) -> None:
+    if isinstance(attention_mask, TamdMask) and attention_mask.kv_len is not None:
+        raise TamdError("a decode-step mask (key counts in device memory) reached a fused block that does not implement it "
+                        "(supported: the registered attention function and the cached Llama path)")
+
+
+def split_mask(attention_mask, batch: int, kv_len: int):
+    """(key_valid [B, kv_len] bool or None, q_start int32 [2, B, S] or None) for the blocks that take these two: a mask that
+    also carries key counts is refused, not cut down."""
+    _refuse_kv_len(attention_mask)
+    return split_mask_kv(attention_mask, batch, kv_len)[:2]
 
 
 _varlen_cache = threading.local()  # the last (cu_seq_lens_q, cu_seq_lens_k, total) -> q_start of this thread
@@ -246,6 +285,7 @@ def _key_valid_from_mask(attention_mask, batch: int, kv_len: int) -> Optional[to
     (two small launches per layer otherwise -- 64 per generated token of a 32-layer model, where a decode step is bound by
     launches).  The entry keeps the mask tensor alive, so `_same_tensor` cannot be fooled by a recycled allocation, and an
     in-place update of the mask changes its version."""
+    _refuse_kv_len(attention_mask)
     src = attention_mask.key_valid if isinstance(attention_mask, TamdMask) else attention_mask
     hit = getattr(_kv_cache, "entry", None)
     ver = _ver(src) if torch.is_tensor(src) else None  # (None: an inference tensor -- converted on every call, never cached)
@@ -263,6 +303,7 @@ def _key_valid_from_mask(attention_mask, batch: int, kv_len: int) -> Optional[to
 
 def _key_valid_from_mask_uncached(attention_mask, batch: int, kv_len: int) -> Optional[torch.Tensor]:
     if isinstance(attention_mask, TamdMask):  # a fused module path that only knows padding masks
+        _refuse_kv_len(attention_mask)
         if attention_mask.q_start is not None:
             raise TamdError("packed sequences reached a fused block that does not implement them (supported: the "
                             "Llama path and every model that goes through the registered attention function)")
@@ -319,7 +360,7 @@ def tamd_attention_forward(module, query, key, value, attention_mask, dropout: f
     if used is not None and used < sk:
         sk = used  # pre-allocated cache: only the first kv_len key slots are in use (strided views of the cache)
         k, v = k[:, :sk], v[:, :sk]
-    key_valid, q_start = split_mask(attention_mask, b, sk)
+    key_valid, q_start, kv_len = split_mask_kv(attention_mask, b, sk)
     q_start = varlen_q_start(q_start, kwargs, b, sq, sk, causal)
     q_start = window_q_start(q_start, kwargs.get("sliding_window"), b, sq, sk, causal, q.device)
     if q.stride(3) != 1:
@@ -328,7 +369,7 @@ def tamd_attention_forward(module, query, key, value, attention_mask, dropout: f
         k = k.contiguous()
     if v.stride(3) != 1:
         v = v.contiguous()
-    out = ops.attention(q, k, v, float(scaling), causal, key_valid, dropout_p=drop_p, q_start=q_start)
+    out = ops.attention(q, k, v, float(scaling), causal, key_valid, dropout_p=drop_p, q_start=q_start, kv_len=kv_len)
     return out, None
 
 

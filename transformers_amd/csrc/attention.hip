@@ -67,15 +67,26 @@ int attn_fwd_launch(const AttnArgs& a, bool causal, hipStream_t s) {
   return launch_status();
 }
 
-// split-KV forward + merge (tamd_attn_decode).  No dropout, no packed sequences (checked by the caller).
+// split-KV forward + merge (tamd_attn_decode).  No dropout, no packed sequences (checked by the caller).  The grid and the
+// workspace follow the plan, which follows seq_k -- the allocation -- also when the key counts come from a.seq_k_dev: a piece
+// whose tiles lie behind its row's count loads nothing and leaves with weight 0.
 template <typename T, int D>
 int attn_decode_launch(const AttnArgs& a, bool causal, hipStream_t s) {
   const size_t smem = (size_t)4 * kKB * D * 2;
   dim3 grid((unsigned)(a.nqt * a.heads_q * a.batch * a.kv_splits)), block(kAttnThreads);
-  if (causal)
-    hipLaunchKernelGGL((attn_fwd_kernel<T, D, true, true, false, true>), grid, block, smem, s, a);
-  else
-    hipLaunchKernelGGL((attn_fwd_kernel<T, D, false, true, false, true>), grid, block, smem, s, a);
+#define TAMD_AD(C_, L_) hipLaunchKernelGGL((attn_fwd_kernel<T, D, C_, true, false, true, L_>), grid, block, smem, s, a)
+  if (a.seq_k_dev != nullptr) {  // key counts in device memory: the DEVLEN instantiations
+    if (causal)
+      TAMD_AD(true, true);
+    else
+      TAMD_AD(false, true);
+  } else {
+    if (causal)
+      TAMD_AD(true, false);
+    else
+      TAMD_AD(false, false);
+  }
+#undef TAMD_AD
   const int rows = a.batch * a.seq_q * a.heads_q;
   hipLaunchKernelGGL((attn_combine_kernel<T, D>), dim3((unsigned)rows), dim3(256), 0, s, a);  // one workgroup per row
   return launch_status();
@@ -148,6 +159,7 @@ AttnArgs make_args(const tamd_attn_params* p) {
   a.lse_part = nullptr;
   a.kv_splits = 1;
   a.tiles_per_split = 0;
+  a.seq_k_dev = nullptr;  // (tamd_attn_decode alone honours tamd_attn_params.seq_k_dev, and sets it there)
 #ifdef TAMD_DIAG
   a.trace = g_attn_trace;
 #else
@@ -179,6 +191,7 @@ extern "C" uint32_t tamd_attn_dropout_field(uint64_t seed, uint64_t batch_head, 
 extern "C" int tamd_attn_fwd(const struct tamd_attn_params* p, tamd_stream_t stream) {
   const int chk = attn_check(p);
   if (chk != TAMD_OK) return chk;
+  if (p->seq_k_dev != nullptr) return TAMD_E_ARG;  // key counts in device memory: tamd_attn_decode (inference) only
   const AttnArgs a = make_args(p);
   hipStream_t s = TAMD_STREAM(stream);
   if (p->head_dim == 128) {
@@ -214,7 +227,8 @@ static DecodePlan decode_plan(const tamd_attn_params* p0) {
     p.heads_q = p.heads_kv;
     p.causal = 0;
   }
-  int64_t kend = p.seq_k;  // (causal: the last query row sees every key of the range; rows before it fewer)
+  int64_t kend = p.seq_k;  // (causal: the last query row sees every key of the range; rows before it fewer.  With seq_k_dev
+                           // this is the allocation: the plan and the workspace do not depend on device data)
   const int64_t nkt = ceil_div(kend, kKB), nqt = ceil_div(p.seq_q, kQB);
   const int64_t base = nqt * p.heads_q * p.batch;
   int64_t splits = ceil_div(768, base);  // ~3 workgroups per CU
@@ -235,7 +249,7 @@ extern "C" int tamd_attn_decode(const struct tamd_attn_params* p0, void* workspa
                                 tamd_stream_t stream) {
   const int chk = attn_check(p0);
   if (chk != TAMD_OK) return chk;
-  if (p0->dropout_p != 0.f || p0->q_start != nullptr) return TAMD_E_ARG;
+  if (p0->dropout_p != 0.f || p0->q_start != nullptr) return TAMD_E_ARG;  // (with or without seq_k_dev)
   if (!workspace) return TAMD_E_NULL;
   if (workspace_bytes < tamd_attn_decode_workspace_bytes(p0) || !aligned16(workspace)) return TAMD_E_WORKSPACE;
   const DecodePlan d = decode_plan(p0);
@@ -243,6 +257,7 @@ extern "C" int tamd_attn_decode(const struct tamd_attn_params* p0, void* workspa
   a.xcd_map = 0;
   a.kv_splits = d.splits;
   a.tiles_per_split = d.tiles_per_split;
+  a.seq_k_dev = reinterpret_cast<const int*>(d.p.seq_k_dev);  // (decode_plan re-strides rows and heads, never the batch)
   const size_t rows = (size_t)d.splits * (size_t)d.p.batch * (size_t)d.p.seq_q * (size_t)d.p.heads_q;
   a.o_part = reinterpret_cast<float*>(workspace);
   a.lse_part = a.o_part + rows * (size_t)d.p.head_dim;
@@ -259,6 +274,7 @@ extern "C" int tamd_attn_bwd(const struct tamd_attn_bwd_params* p, tamd_stream_t
   if (!p) return TAMD_E_NULL;
   const int chk = attn_check(&p->fwd);
   if (chk != TAMD_OK) return chk;
+  if (p->fwd.seq_k_dev != nullptr) return TAMD_E_ARG;  // (an inference feature: tamd_attn_decode)
   if (!p->dout || !p->dq || !p->dk || !p->dv || !p->delta || !p->fwd.lse) return TAMD_E_NULL;
   if ((p->rope_cos != nullptr) != (p->rope_sin != nullptr)) return TAMD_E_NULL;
   if (p->rope_cos != nullptr) {  // rotary on the way out: heads of 128, positions = row indices (no KV offset)

@@ -47,6 +47,10 @@ struct AttnArgs {
   float* o_part;
   float* lse_part;
   int kv_splits, tiles_per_split;
+  // split-KV forward only (the DEVLEN instantiations): the key count of every batch row in device memory (int32 [batch],
+  // tamd_attn_params.seq_k_dev), or null.  Row b is the problem with clamp(seq_k_dev[b], 0, seq_k) keys; seq_k stays the
+  // allocation (plan, key_valid stride)
+  const int* seq_k_dev;
 };
 
 // Diagnostic build only: phase i of the forward tile loop ends here (s_memtime stamps of workgroup 0, summed per wave)
@@ -344,6 +348,16 @@ __device__ __forceinline__ f32x16 splat16(float v) {
   asm volatile("" : "+v"(t));
 #endif
   return t;
+}
+
+// a value every lane of the wave holds, as a provably wave-uniform (SGPR) one: what a buffer size or a trip count is derived
+// from (a VGPR there makes the buffer descriptor a waterfall loop per load)
+__device__ __forceinline__ int wave_uniform_i32(int v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_readfirstlane(v);
+#else
+  return v;
+#endif
 }
 
 // first visible key of query row `qrow` (0 when sequences are not packed) and its wave-wide max / min

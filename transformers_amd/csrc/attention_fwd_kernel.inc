@@ -8,7 +8,12 @@
 // the other workgroup already fills those gaps.)
 // SPLIT (tamd_attn_decode): the key range is cut into a.kv_splits pieces, one workgroup each; a piece leaves as normalised
 // fp32 rows + their log-sum-exp (a.o_part / a.lse_part) for attn_combine_kernel instead of as O / LSE.
-template <typename T, int D, bool CAUSAL, bool HAS_MASK, bool DROP, bool SPLIT = false>
+// DEVLEN (SPLIT only; a.seq_k_dev): the number of keys of a batch row comes from device memory (a pre-allocated KV cache): every
+// piece of geometry below uses that count, so the tiles behind it are neither loaded nor visited and the pieces that own them
+// leave as "saw no key".  (A template argument, not a test of the pointer inside the SPLIT kernels: with the test there the
+// calls WITHOUT counts ran 0.4 us slower at every shape and 1.4 us at 8 query rows x 4096 keys, 23.5 against 22.1 -- the same
+// loop, another order of the prologue's scalar loads; as it is they run the code they ran before.)
+template <typename T, int D, bool CAUSAL, bool HAS_MASK, bool DROP, bool SPLIT = false, bool DEVLEN = false>
 // (two workgroups per CU where the registers allow it: the dropout variants at D = 128 need more than 256)
 // (three at head_dim 64 without padding mask / dropout -- CLIP: the kernel sat at 155 registers before the resident -m tuple)
 __global__ __launch_bounds__(kAttnThreads, (DROP && D > 64) ? 1 : ((D == 64 && !HAS_MASK && !DROP) ? 3 : 2)) void attn_fwd_kernel(AttnArgs a) {
@@ -45,7 +50,16 @@ __global__ __launch_bounds__(kAttnThreads, (DROP && D > 64) ? 1 : ((D == 64 && !
   }
   const int hkv = h / group;
   const int q0 = qt * kQB;
-  const int off = a.seq_k - a.seq_q;  // causal: key k visible to query s iff k <= s + off
+  // the keys of this batch row: all of them, or (DEVLEN) the count in device memory, clamped to the allocation.  b is
+  // workgroup-uniform: one load, made wave-uniform before anything is derived from it, and two scalar selects (see tile_rows)
+  static_assert(!DEVLEN || SPLIT, "key counts in device memory: the split-KV instantiations only");
+  int seq_k = a.seq_k;
+  if constexpr (SPLIT && DEVLEN) {
+    int n = wave_uniform_i32(a.seq_k_dev[b]);
+    n = n < a.seq_k ? n : a.seq_k;
+    seq_k = n > 0 ? n : 0;
+  }
+  const int off = seq_k - a.seq_q;  // causal: key k visible to query s iff k <= s + off
   const T* Q = reinterpret_cast<const T*>(a.q) + (int64_t)b * a.qsb + (int64_t)h * a.qsh;
   const T* K = reinterpret_cast<const T*>(a.k) + (int64_t)b * a.ksb + (int64_t)hkv * a.ksh;
   const T* V = reinterpret_cast<const T*>(a.v) + (int64_t)b * a.vsb + (int64_t)hkv * a.vsh;
@@ -76,7 +90,7 @@ __global__ __launch_bounds__(kAttnThreads, (DROP && D > 64) ? 1 : ((D == 64 && !
   // exponentials refer to, 0 while the row has seen no visible key); rewritten only when the deferred rescale fires
   f32x16 neg_m = splat16(0.f);
 
-  int kend = a.seq_k;
+  int kend = seq_k;
   if (CAUSAL) {
     const int lim = q0 + kQB - 1 + off + 1;  // keys visible to the last query row of the block
     kend = lim < kend ? lim : kend;
@@ -112,7 +126,7 @@ __global__ __launch_bounds__(kAttnThreads, (DROP && D > 64) ? 1 : ((D == 64 && !
   };
   // rows of tile t < ceil(seq_k / 64) (a scalar min, never a two-sided clamp: hipcc makes that a v_med3_i32 -- a VGPR -- and the
   // buffer descriptor built from it a waterfall loop per piece)
-  auto tile_rows = [&](int t) { return a.seq_k - t * kKB < kKB ? a.seq_k - t * kKB : kKB; };
+  auto tile_rows = [&](int t) { return seq_k - t * kKB < kKB ? seq_k - t * kKB : kKB; };
   auto issue = [&](int t, int rows, int buf) {
 #pragma unroll
     for (int n = 0; n < 2 * TileFeed<D>::NI; ++n) issue_piece(t, rows, buf, n);
@@ -190,9 +204,9 @@ __global__ __launch_bounds__(kAttnThreads, (DROP && D > 64) ? 1 : ((D == 64 && !
       unsigned long long vmask = ~0ull;
       if (HAS_MASK) {
         const int kp = kt0 + lane;
-        vmask = ballot64(kp < a.seq_k && (a.key_valid == nullptr || a.key_valid[(int64_t)b * a.seq_k + kp] != 0));
+        vmask = ballot64(kp < seq_k && (a.key_valid == nullptr || a.key_valid[(int64_t)b * a.seq_k + kp] != 0));  // (rows of the plane: the allocation)
       }
-      const bool need_mask = (HAS_MASK && vmask != ~0ull) || (kt0 + kKB > a.seq_k) || (CAUSAL && (kt0 + kKB - 1 > qw0 + off)) ||
+      const bool need_mask = (HAS_MASK && vmask != ~0ull) || (kt0 + kKB > seq_k) || (CAUSAL && (kt0 + kKB - 1 > qw0 + off)) ||
                              (kt0 < klo_max);
       if (need_mask) {
 #pragma unroll
@@ -201,7 +215,7 @@ __global__ __launch_bounds__(kAttnThreads, (DROP && D > 64) ? 1 : ((D == 64 && !
           for (int r = 0; r < 16; ++r) {
             const int kl = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;  // key index inside the tile
             const int kp = kt0 + kl;
-            bool vis = kp < a.seq_k && kp >= klo;
+            bool vis = kp < seq_k && kp >= klo;
             if (CAUSAL) vis = vis && (kp <= qrow + off);
             if (HAS_MASK) vis = vis && ((vmask >> kl) & 1ull);
             s[sub][r] = vis ? s[sub][r] : -INFINITY;

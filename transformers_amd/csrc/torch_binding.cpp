@@ -903,7 +903,8 @@ bool swiglu_bwd_fused(const Tensor& dy, const Tensor& wd, const Tensor& gu) {
 // ---- attention
 void fill_attn_params(tamd_attn_params* ap, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
                       const Tensor& lse, const Tensor& key_valid, double scale, bool causal, double dropout_p, int64_t seed,
-                      const Tensor& q_start, bool q_prescaled = false, const uint64_t* seed_dev = nullptr) {
+                      const Tensor& q_start, bool q_prescaled = false, const uint64_t* seed_dev = nullptr,
+                      const Tensor& kv_len = Tensor()) {
   ap->q = ptr(q);
   ap->k = ptr(k);
   ap->v = ptr(v);
@@ -930,6 +931,7 @@ void fill_attn_params(tamd_attn_params* ap, const Tensor& q, const Tensor& k, co
   ap->q_start = (const int32_t*)ptr(q_start);
   ap->q_prescaled = q_prescaled ? 1 : 0;
   ap->dropout_seed_dev = seed_dev;
+  ap->seq_k_dev = (const int32_t*)ptr(kv_len);  // (undefined: NULL -- every caller but the inference forward)
 }
 
 // word `site` of a device-resident seed tensor (int64, ops.dropout_seed_tensor) or NULL: graph-replay-safe dropout
@@ -965,20 +967,33 @@ Tensor checked_q_start(const OptTensor& q_start, const Tensor& q, bool causal) {
   return contig(*q_start);
 }
 
+// key counts in device memory (include/tamd.h seq_k_dev): int32 [batch] on the operands' device
+Tensor checked_kv_len(const OptTensor& kv_len, const Tensor& q) {
+  if (!kv_len) return Tensor();
+  TORCH_CHECK(kv_len->scalar_type() == at::kInt && kv_len->dim() == 1 && kv_len->size(0) == q.size(0),
+              "tamd: kv_len must be int32 [batch] = [", q.size(0), "], got ", kv_len->scalar_type(), " ", kv_len->sizes());
+  TORCH_CHECK(kv_len->device() == q.device(), "tamd: kv_len lives on ", kv_len->device(), ", the attention operands on ",
+              q.device());
+  return contig(*kv_len);
+}
+
 // q [B,Sq,Hq,D], k/v [B,Sk,Hkv,D] (strided views fine) -> o [B,Sq,Hq,D] contiguous, lse [B,Hq,Sq] fp32 or undefined
 std::tuple<Tensor, Tensor> k_attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal,
                                       const OptTensor& key_valid_, bool need_lse, double dropout_p, int64_t seed,
                                       const OptTensor& q_start_, bool q_prescaled = false,
-                                      const uint64_t* seed_dev = nullptr) {
-  Launch L({&q, &k, &v, p(key_valid_)});
+                                      const uint64_t* seed_dev = nullptr, const OptTensor& kv_len_ = {}) {
+  Launch L({&q, &k, &v, p(key_valid_), p(kv_len_)});
   Tensor o = at::empty({q.size(0), q.size(1), q.size(2), q.size(3)}, q.options());
   Tensor lse = need_lse ? f32_like(q, {q.size(0), q.size(2), q.size(1)}) : Tensor();
   Tensor key_valid = checked_key_valid(key_valid_, q, k);
   Tensor q_start = checked_q_start(q_start_, q, causal);
-  tamd_attn_params ap;
-  fill_attn_params(&ap, q, k, v, o, lse, key_valid, scale, causal, dropout_p, seed, q_start, q_prescaled, seed_dev);
-  // decode shapes (a KV cache: a few query rows over a long key range) take the split-KV schedule
-  if (kDecodeKernel && q.size(1) <= kDecodeMaxRows && k.size(1) >= kDecodeMinKeys && dropout_p == 0.0 && !q_start.defined()) {
+  Tensor kv_len = checked_kv_len(kv_len_, q);
+  tamd_attn_params ap{};
+  fill_attn_params(&ap, q, k, v, o, lse, key_valid, scale, causal, dropout_p, seed, q_start, q_prescaled, seed_dev, kv_len);
+  // decode shapes (a KV cache: a few query rows over a long key range) take the split-KV schedule; key counts in device
+  // memory exist in that kernel alone: such a call takes it whatever its shape (and is refused there with dropout / q_start)
+  if (kv_len.defined() ||
+      (kDecodeKernel && q.size(1) <= kDecodeMaxRows && k.size(1) >= kDecodeMinKeys && dropout_p == 0.0 && !q_start.defined())) {
     const size_t nbytes = api().tamd_attn_decode_workspace_bytes(&ap);
     Tensor ws = at::empty({(int64_t)nbytes}, q.options().dtype(at::kByte));
     check(api().tamd_attn_decode(&ap, mptr(ws), nbytes, L.stream), "tamd_attn_decode");
@@ -1009,7 +1024,7 @@ std::tuple<Tensor, Tensor, Tensor> k_attn_bwd(const Tensor& q, const Tensor& k, 
   auto dshape = lse.sizes().vec();
   dshape.insert(dshape.begin(), 2);
   Tensor delta = at::empty(dshape, lse.options());  // -delta | -lse*log2(e) (written by the dQ kernel)
-  tamd_attn_bwd_params bp;
+  tamd_attn_bwd_params bp{};
   fill_attn_params(&bp.fwd, q, k, v, o, lse, key_valid, scale, causal, dropout_p, seed, q_start, q_prescaled, seed_dev);
   bp.dout = ptr(dout);
   bp.dq = mptr(dq);
@@ -1129,9 +1144,10 @@ Tensor attn_operand(const Tensor& t) {
 }
 std::tuple<Tensor, Tensor> op_attn_fwd(const Tensor& q_, const Tensor& k_, const Tensor& v_, double scale, bool causal,
                                        const OptTensor& key_valid, bool need_lse, double dropout_p, int64_t seed,
-                                       const OptTensor& q_start, const OptTensor& seed_dev) {
+                                       const OptTensor& q_start, const OptTensor& seed_dev, const OptTensor& kv_len) {
   const Tensor q = attn_operand(q_), k = attn_operand(k_), v = attn_operand(v_);
-  auto [o, lse] = k_attn_fwd(q, k, v, scale, causal, key_valid, need_lse, dropout_p, seed, q_start, false, seed_word(seed_dev, 0));
+  auto [o, lse] = k_attn_fwd(q, k, v, scale, causal, key_valid, need_lse, dropout_p, seed, q_start, false, seed_word(seed_dev, 0),
+                             kv_len);
   return {o, lse.defined() ? lse : nothing(q)};
 }
 std::tuple<Tensor, Tensor, Tensor> op_attn_bwd(const Tensor& q_, const Tensor& k_, const Tensor& v_, const Tensor& o_,
@@ -1232,9 +1248,13 @@ Tensor op_rope(const Tensor& x, const Tensor& cos, const Tensor& sin, int64_t nh
 
 std::tuple<Tensor, Tensor> op_attention(const Tensor& q_, const Tensor& k_, const Tensor& v_, const OptTensor& key_valid,
                                         double scale, bool causal, double dropout_p, int64_t seed, const OptTensor& q_start,
-                                        bool train, const OptTensor& seed_dev) {
+                                        bool train, const OptTensor& seed_dev, const OptTensor& kv_len) {
+  // key counts in device memory: the split-KV kernel has no backward -- a call that will be differentiated is refused here,
+  // not answered with an lse of another problem
+  TORCH_CHECK(!(kv_len.has_value() && train), "tamd: attention with kv_len is an inference path (train must be false)");
   const Tensor q = attn_operand(q_), k = attn_operand(k_), v = attn_operand(v_);  // (the backward goes through op_attn_bwd: same copies)
-  auto [o, lse] = k_attn_fwd(q, k, v, scale, causal, key_valid, train, dropout_p, seed, q_start, false, seed_word(seed_dev, 0));
+  auto [o, lse] = k_attn_fwd(q, k, v, scale, causal, key_valid, train, dropout_p, seed, q_start, false, seed_word(seed_dev, 0),
+                             kv_len);
   return {o, lse.defined() ? lse : nothing(q)};
 }
 
@@ -1627,7 +1647,7 @@ TORCH_LIBRARY(tamd, m) {
   m.def("gemm_dw_group(Tensor[] dy, Tensor[] x) -> Tensor[]");
   m.def("gemm_colscale(Tensor x2, Tensor w, Tensor? bias, int scale_cols, float col_scale) -> Tensor");
   m.def("attn_fwd(Tensor q, Tensor k, Tensor v, float scale, bool causal, Tensor? key_valid=None, bool need_lse=True, "
-        "float dropout_p=0.0, int seed=0, Tensor? q_start=None, Tensor? seed_dev=None) -> (Tensor, Tensor)");
+        "float dropout_p=0.0, int seed=0, Tensor? q_start=None, Tensor? seed_dev=None, Tensor? kv_len=None) -> (Tensor, Tensor)");
   m.def("attn_bwd(Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor dout, float scale, bool causal, "
         "Tensor? key_valid=None, float dropout_p=0.0, int seed=0, Tensor? q_start=None, Tensor? rope_cos=None, "
         "Tensor? rope_sin=None, Tensor? seed_dev=None) -> (Tensor, Tensor, Tensor)");
@@ -1646,7 +1666,7 @@ TORCH_LIBRARY(tamd, m) {
   m.def("conv1d(Tensor x, Tensor w, Tensor? b) -> Tensor");
   m.def("rope(Tensor x, Tensor cos, Tensor sin, int nheads, int head_dim, bool conj=False) -> Tensor");
   m.def("attention(Tensor q, Tensor k, Tensor v, Tensor? key_valid, float scale, bool causal, float dropout_p, int seed, "
-        "Tensor? q_start, bool train, Tensor? seed_dev=None) -> (Tensor, Tensor)");
+        "Tensor? q_start, bool train, Tensor? seed_dev=None, Tensor? kv_len=None) -> (Tensor, Tensor)");
   m.def("swiglu(Tensor gu) -> Tensor");
   m.def("bias_act(Tensor x, Tensor? bias, int act) -> Tensor");
   m.def("embedding(Tensor ids, Tensor table, int padding_idx=-1) -> Tensor");

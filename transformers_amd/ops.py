@@ -295,10 +295,13 @@ def raw_gemm_swiglu_bwd(dy, wd, gu):
     return T.gemm_swiglu_bwd(dy, wd, gu)
 
 
-def raw_attn_fwd(q, k, v, scale, causal, key_valid=None, need_lse=True, dropout_p=0.0, seed=0, q_start=None, seed_dev=None):
-    """q [B,Sq,Hq,D], k/v [B,Sk,Hkv,D] (strided views fine) -> o [B,Sq,Hq,D] contiguous, lse [B,Hq,Sq] fp32."""
+def raw_attn_fwd(q, k, v, scale, causal, key_valid=None, need_lse=True, dropout_p=0.0, seed=0, q_start=None, seed_dev=None,
+                 kv_len=None):
+    """q [B,Sq,Hq,D], k/v [B,Sk,Hkv,D] (strided views fine) -> o [B,Sq,Hq,D] contiguous, lse [B,Hq,Sq] fp32.
+    kv_len (int32 [B] on the device, or None): the key slots in use per batch row -- k / v are a pre-allocated cache, row b is
+    computed as if they had been sliced to kv_len[b] rows (include/tamd.h seq_k_dev; always the split-KV decode kernel)."""
     o, lse = T.attn_fwd(q, k, v, float(scale), bool(causal), key_valid, need_lse, float(dropout_p),
-                        int(seed) & 0x7FFFFFFFFFFFFFFF, q_start, seed_dev)
+                        int(seed) & 0x7FFFFFFFFFFFFFFF, q_start, seed_dev, kv_len)
     return o, (lse if need_lse else None)
 
 
@@ -407,7 +410,8 @@ register("gemm_out", lambda out, a, b, a_km=False, b_kn=False, bias=None, residu
 register("gemm_swiglu", lambda x2, wgu, need_gu=True: (x2.new_empty(x2.shape[0], wgu.shape[0]) if need_gu else _nothing(x2),
                                                        x2.new_empty(x2.shape[0], wgu.shape[0] // 2)))
 register("gemm_swiglu_bwd", lambda dy, wd, gu: torch.empty_like(gu))
-register("attn_fwd", lambda q, k, v, scale, causal, key_valid=None, need_lse=True, dropout_p=0.0, seed=0, q_start=None, seed_dev=None: (
+register("attn_fwd", lambda q, k, v, scale, causal, key_valid=None, need_lse=True, dropout_p=0.0, seed=0, q_start=None, seed_dev=None,
+         kv_len=None: (
     q.new_empty(q.shape), _f32(q, q.shape[0], q.shape[2], q.shape[1]) if need_lse else _nothing(q)))
 register("attn_bwd", lambda q, k, v, o, lse, dout, scale, causal, key_valid=None, dropout_p=0.0, seed=0, q_start=None,
          rope_cos=None, rope_sin=None, seed_dev=None: (
@@ -623,14 +627,14 @@ register("rope", lambda x, cos, sin, nheads, head_dim, conj=False: torch.empty_l
 # softmax(scale QK^T + mask) V on [B,S,H,D] views.  Reference: eager_attention_forward,
 # models/llama/modeling_llama.py:191-213 and siblings.
 def _attention_setup(ctx, inputs, output):
-    q, k, v, key_valid, scale, causal, dropout_p, seed, q_start, _train, seed_dev = inputs
+    q, k, v, key_valid, scale, causal, dropout_p, seed, q_start, _train, seed_dev, _kv_len = inputs
     ctx.save_for_backward(q, k, v, output[0], output[1], key_valid, q_start, seed_dev)
     ctx.meta = (scale, causal, dropout_p, seed)
     ctx.set_materialize_grads(False)
 
 
 def _attention_backward(ctx, do, _dlse):
-    none = (None,) * 11
+    none = (None,) * 12
     if do is None:
         return none
     q, k, v, o, lse, key_valid, q_start, seed_dev = ctx.saved_tensors
@@ -641,7 +645,7 @@ def _attention_backward(ctx, do, _dlse):
     return (dq, dk, dv) + none[3:]
 
 
-register("attention", lambda q, k, v, key_valid, scale, causal, dropout_p, seed, q_start, train, seed_dev=None: (
+register("attention", lambda q, k, v, key_valid, scale, causal, dropout_p, seed, q_start, train, seed_dev=None, kv_len=None: (
     q.new_empty(q.shape), _f32(q, q.shape[0], q.shape[2], q.shape[1]) if train else _nothing(q)),
     _attention_backward, _attention_setup)
 
@@ -979,11 +983,16 @@ def dropout_keep_mask(seed: int, batch: int, heads: int, seq_q: int, seq_k: int,
     return torch.from_numpy((field >= thr16).reshape(batch, heads, seq_q, seq_k))
 
 
-def attention(q, k, v, scale, causal, key_valid=None, dropout_p=0.0, seed=None, q_start=None, seed_dev=None):
+def attention(q, k, v, scale, causal, key_valid=None, dropout_p=0.0, seed=None, q_start=None, seed_dev=None, kv_len=None):
+    """kv_len (int32 [B] on the device, or None): k / v are a pre-allocated cache of which row b uses the first kv_len[b] slots
+    (see raw_attn_fwd) -- inference only: a call that would be differentiated is refused."""
     if dropout_p > 0.0 and seed is None and seed_dev is None:
         (seed,), seed_dev = dropout_seeds(1, q.device)
+    train = _wants_grad(q, k, v)
+    if kv_len is not None and train:
+        raise TamdError("attention over key counts in device memory (kv_len) is an inference path: it has no backward")
     return T.attention(q, k, v, key_valid, float(scale), bool(causal), float(dropout_p), int(seed or 0), q_start,
-                       _wants_grad(q, k, v), seed_dev)[0]
+                       train, seed_dev, kv_len)[0]
 
 
 def packed_q_start(seq_ids: torch.Tensor) -> torch.Tensor:
