@@ -2,7 +2,11 @@
 SAME (storage-dtype-rounded) inputs.  The tolerance for floating-point ops is 1e-3 norm-relative
 unless the op's output rounding dominates (then 2^-8 relative = one bf16 ulp); integer / index paths
 (embedding gather, label handling) are bit-exact.  Each test runs twice: under the CPU execution model
-(`emu`, not gpu) and on the MI355X (`hip`, gpu)."""
+(`emu`, not gpu) and on the MI355X (`hip`, gpu).
+
+The shapes here grow with `env.big`, so the MI355X sees round shapes only and every gate is a norm.  The row kernels (norm
+family, cross-entropy, column sums) are checked a second time in test_row_kernels.py, which runs identical small shapes on
+both backends -- every norm geometry, ragged rows and widths -- and checks per element."""
 import math
 
 import pytest
