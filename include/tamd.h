@@ -226,7 +226,8 @@ enum tamd_gemm_epilogue {
   TAMD_EPI_BIAS = 1,      /* C = round(acc + bias[n])                        nn.Linear with bias           */
   TAMD_EPI_RESIDUAL = 2,  /* C = round(round(acc [+bias]) + R[m,n])          o_proj/down_proj + residual   */
   TAMD_EPI_BIAS_ACT = 3,  /* C = round(act(round(acc + bias)))               BertIntermediate              */
-  TAMD_EPI_ACCUM = 4      /* C = round(acc + C_old[m,n])  (gradient accumulation into an existing .grad)   */
+  TAMD_EPI_ACCUM = 4      /* C = round(round(acc) + C_old[m,n])   gradient accumulation into an existing .grad: the  */
+                          /* bits of the plain product followed by an in-place add (two roundings, as RESIDUAL)      */
 };
 
 /* C[M,N] = A[M,K] . B[N,K]^T  with fp32 MFMA accumulation: nn.Linear forward

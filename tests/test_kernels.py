@@ -6,7 +6,9 @@ unless the op's output rounding dominates (then 2^-8 relative = one bf16 ulp); i
 
 The shapes here grow with `env.big`, so the MI355X sees round shapes only and every gate is a norm.  The row kernels (norm
 family, cross-entropy, column sums) are checked a second time in test_row_kernels.py, which runs identical small shapes on
-both backends -- every norm geometry, ragged rows and widths -- and checks per element."""
+both backends -- every norm geometry, ragged rows and widths -- and checks per element.  The GEMM family (tile kernels,
+weight-streaming kernels, split-K, segmented and grouped launches, every epilogue) is checked bit for bit against exact
+float64 chains, at ragged edges and with leading dimensions, in test_gemm_elements.py."""
 import math
 
 import pytest

@@ -35,17 +35,12 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import record
+from kernel_checks import BF16, F16, F32, NAME, Guarded, check, rnd, ulp  # (shared with tests/test_gemm_elements.py)
 from transformers_amd import ops
 
-BF16, F16, F32 = torch.bfloat16, torch.float16, torch.float32
-MANT = {BF16: 7, F16: 10, F32: 23}
-MINEXP = {BF16: -126, F16: -14, F32: -126}
 VE = {BF16: 8, F16: 8, F32: 4}  # elements of a 16-byte vector
-NAME = {BF16: "bf16", F16: "fp16", F32: "fp32"}
 U2 = 2.0 ** -23
 EPS = float(np.float32(1e-5))  # what the kernels receive
-SENT = -3.0
 E_SHAPE, E_ARG = -2, -6
 MAX_PARTIALS = 512  # csrc/colsum.h kNormMaxPartials: blocks of a norm backward
 
@@ -61,61 +56,6 @@ def geometry(cols, dtype):
     if per > 8:
         return None
     return (1 if per <= 1 else 2 if per <= 2 else 4 if per <= 4 else 8), wpr
-
-
-# ---------------------------------------------------------------------------------------------------- the bound
-def ulp(ref, dtype):
-    m, e = torch.frexp(ref.abs())  # |ref| = m * 2^e, m in [0.5, 1)
-    e = torch.where(ref != 0, e.to(torch.int64) - 1, torch.full_like(e, MINEXP[dtype], dtype=torch.int64))
-    return torch.ldexp(torch.ones_like(ref), e.clamp_min(MINEXP[dtype]) - MANT[dtype])
-
-
-def rnd(t64, dtype):
-    return t64.to(dtype).double()
-
-
-_WORST = {}
-
-
-def check(name, got, ref, s, dtype, chain=None):
-    """Every element of `got` within the gate of the module docstring; `chain`: the reference rounded as the kernel
-    documents (default: once to the storage type)."""
-    got = got.detach().cpu().double()
-    assert got.shape == ref.shape, (name, got.shape, ref.shape)
-    unit = ulp(ref, dtype) + s
-    own = (((rnd(ref, dtype) if chain is None else chain) - ref).abs() / unit).max().item()
-    gate = 2.0 * max(0.5, own)
-    ratio = (got - ref).abs() / unit
-    worst = ratio.max().item()
-    key = f"{name}[{NAME[dtype]}]"
-    w = _WORST.setdefault(key, [0.0, 0.0, 0.0])
-    w[0], w[1], w[2] = max(w[0], worst if worst == worst else float("inf")), max(w[1], gate), max(w[2], own)
-    record("row_kernels", key, w[0], w[1])
-    record("row_kernels", key + " reference's own rounding", w[2])
-    print(f"{key}: worst {worst:.3f} gate {gate:.3f} (reference's own {own:.3f}) over {got.numel()} elements")
-    if not worst <= gate:  # (NaN fails)
-        bad = torch.nonzero(~(ratio <= gate))
-        i = tuple(bad[0].tolist())
-        raise AssertionError(f"{key}: {bad.shape[0]} of {got.numel()} elements beyond {gate:.3f} x (ulp + s); first at {i}: "
-                             f"got {got[i].item()!r} want {ref[i].item()!r} unit {unit[i].item():.3e}; worst {worst:.3f}")
-
-
-# ---------------------------------------------------------------------------------------------------- guarded outputs
-class Guarded:
-    """`n` elements in the middle of a buffer filled with a sentinel, `guard` elements on either side."""
-
-    def __init__(self, shape, dtype, device, guard):
-        n = int(np.prod(shape))
-        self.guard = guard
-        self.buf = torch.full((n + 2 * guard,), SENT, dtype=dtype, device=device)
-        self.t = self.buf[guard:guard + n].view(*shape)
-
-    def intact(self):
-        g = self.guard
-        return bool((self.buf[:g] == SENT).all()) and bool((self.buf[-g:] == SENT).all())
-
-    def untouched(self):
-        return bool((self.buf == SENT).all())
 
 
 def ptr(t):
