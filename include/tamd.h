@@ -226,8 +226,9 @@ enum tamd_gemm_epilogue {
   TAMD_EPI_BIAS = 1,      /* C = round(acc + bias[n])                        nn.Linear with bias           */
   TAMD_EPI_RESIDUAL = 2,  /* C = round(round(acc [+bias]) + R[m,n])          o_proj/down_proj + residual   */
   TAMD_EPI_BIAS_ACT = 3,  /* C = round(act(round(acc + bias)))               BertIntermediate              */
-  TAMD_EPI_ACCUM = 4      /* C = round(round(acc) + C_old[m,n])   gradient accumulation into an existing .grad: the  */
+  TAMD_EPI_ACCUM = 4,     /* C = round(round(acc) + C_old[m,n])   gradient accumulation into an existing .grad: the  */
                           /* bits of the plain product followed by an in-place add (two roundings, as RESIDUAL)      */
+  TAMD_EPI_SWIGLU = 5     /* tamd_gemm_routed only: the way out of tamd_gemm_swiglu (B = a fused [gate ; up] weight)  */
 };
 
 /* C[M,N] = A[M,K] . B[N,K]^T  with fp32 MFMA accumulation: nn.Linear forward
@@ -308,6 +309,67 @@ int tamd_gemm_swiglu(const void* X, const void* Wgu, void* GU, void* ACT, int64_
  * read back per Llama-3-8B layer at 8 x 4096 otherwise).  K % 64 == 0, I % 8 == 0; dGU must not alias GU. */
 int tamd_gemm_swiglu_bwd(const void* dY, const void* Wd, const void* GU, void* dGU, int64_t M, int64_t I, int64_t K,
                          int64_t lddy, int64_t ldw, int64_t ldgu, int64_t lddgu, int dtype, tamd_stream_t stream);
+
+/* ------------------------------------------------------------------ sparse mixture-of-experts (routing + routed GEMM) */
+
+/* The experts of a gated sparse-MoE block -- MixtralExperts.forward, models/mixtral/modeling_mixtral.py (the eager
+ * per-expert loop: one_hot / where / index_add_), dispatched through integrations/moe.py (ALL_EXPERTS_FUNCTIONS,
+ * grouped_mm_experts_forward: argsort / histc / index_select, `_grouped_mm`, index_add) -- on expert-sorted buffers whose
+ * layout lives in DEVICE memory: no host synchronisation, no atomics, deterministic.
+ *
+ * S = tokens * top_k (token, slot) pairs, E = experts <= 256.  Every expert owns one segment of rows of the sorted buffers;
+ * segments are padded to multiples of 64 rows (whole K stages of the weight-gradient products), so the buffers have
+ *     rows_pad >= S + 63 E rounded up to 64       rows -- known to the host without reading the device.
+ *
+ * tamd_moe_route, the plan (moe.py: `sort` / `histc` / `cumsum` of grouped_mm_experts_forward), from top_k_index int64 [tokens, top_k]:
+ *   count[E]      pairs per expert
+ *   offset[E+1]   exclusive prefix sum of the counts, each rounded up to a multiple of 64
+ *   pos[tokens, top_k]   row of the pair in the sorted buffers = offset[e] + rank, rank = the pair's rank inside its expert in
+ *                 ascending (token, slot) order (a stable sort: the summation order of the weight gradients is fixed)
+ *   tiles[E + 1 + max_tiles], max_tiles = ceil((rows_pad + 192 E) / 256): tiles[e] = first 256-row tile of expert e among
+ *                 the row tiles of all experts (tiles[E] = their number), tiles[E + 1 + j] = expert of row tile j, -1 behind
+ *                 the last one -- what a workgroup of tamd_gemm_routed reads.
+ * An id outside [0, E) (moe.py's expert-parallel sentinel) gets pos = -1, is counted nowhere, contributes zero everywhere
+ * and never indexes memory.  All int32.  workspace: tamd_moe_route_workspace_bytes() bytes. */
+size_t tamd_moe_route_workspace_bytes(int64_t tokens, int64_t top_k, int64_t experts);
+int tamd_moe_route(const int64_t* top_k_index, int32_t* count, int32_t* offset, int32_t* pos, int32_t* tiles,
+                   void* workspace, size_t workspace_bytes, int64_t tokens, int64_t top_k, int64_t experts,
+                   int64_t rows_pad, tamd_stream_t stream);
+
+/* xs[pos[t, j], :] = x[t, :]  (moe.py: `hidden_states[token_idx]` / index_select) in 16-byte pieces; xs [rows_pad, hidden];
+ * EVERY row of xs that no pair owns (segment padding and the rows behind offset[E]) is written as zeros by this call.
+ * hidden % 8 == 0 (the products of tamd_gemm_routed need K % 64 == 0); bf16 / f16. */
+int tamd_moe_gather(const void* x, const int32_t* pos, const int32_t* count, const int32_t* offset, void* xs, int64_t tokens,
+                    int64_t top_k, int64_t experts, int64_t hidden, int64_t rows_pad, int dtype, tamd_stream_t stream);
+
+/* out[t] = rT( sum_j r32( w[t, j] * f32(ys[pos[t, j]]) ) )  (moe.py: `* top_k_weights` and index_add_ / the sum over slots):
+ * j ascending, every term an fp32 multiply followed by an fp32 add (no contraction), ONE rounding to the storage type at the
+ * end -- the products stay in fp32 where the reference rounds each to the storage type before its sum.  pos = -1: skipped.
+ * w [tokens, top_k] in w_dtype = TAMD_F32 or `dtype`; w == NULL: unit weights (the gradient of tamd_moe_gather:
+ * dx[t] = rT(sum_j f32(dxs[pos[t, j]]))). */
+int tamd_moe_combine(const void* ys, const int32_t* pos, const void* w, void* out, int64_t tokens, int64_t top_k,
+                     int64_t hidden, int w_dtype, int dtype, tamd_stream_t stream);
+
+/* Backward of tamd_moe_combine (autograd of moe.py's weighted sum):
+ *   dys[pos[t, j]] = rT(w[t, j] * f32(dout[t]))      rows no pair owns: zeros, as in tamd_moe_gather
+ *   dw[t, j]       = sum_h f32(dout[t, h]) * f32(ys[pos[t, j], h])    fp32, fixed reduction order, stored in w_dtype; 0 for pos = -1 */
+int tamd_moe_combine_bwd(const void* dout, const void* ys, const int32_t* pos, const void* w, const int32_t* count,
+                         const int32_t* offset, void* dys, void* dw, int64_t tokens, int64_t top_k, int64_t experts,
+                         int64_t hidden, int64_t rows_pad, int w_dtype, int dtype, tamd_stream_t stream);
+
+/* The experts' products (moe.py: `_grouped_mm` / the eager loop's nn.functional.linear per expert; MixtralExperts
+ * gate_up_proj [E, 2I, H], down_proj [E, H, I]) as ONE launch of the 256 x 256 full-line kernel over the plan of
+ * tamd_moe_route (`offset`, `tiles`, the same rows_pad and experts).  flags:
+ *   0 / TAMD_GEMM_B_KN  rows routed: C[seg_e, N] = A[seg_e, K] . B_e^T, B_e = B + e * b_stride elements ([N, K] rows, or [K, N]
+ *                       with TAMD_GEMM_B_KN: dX), seg_e = rows [offset[e], offset[e+1]); K % 64 == 0; M is ignored.
+ *                       epilogue TAMD_EPI_SWIGLU (flags 0): B_e = gate_up_proj[e] (N = 2I rows), C = GU [rows, 2I] or NULL,
+ *                       C2 = ACT [rows, I] (ldc2), rounded as tamd_gemm_swiglu.
+ *   TAMD_GEMM_A_KM | TAMD_GEMM_B_KN   K routed, the weight gradients: C_e[M, N] = A[seg_e, M]^T . B[seg_e, N],
+ *                       C_e = C + e * M * ldc; K and b_stride are ignored.  An expert without rows gets zeros.
+ * bf16 / f16; N % 8 == 0 (SwiGLU: I % 8 == 0), leading dimensions % 8 == 0, M % 8 == 0 (K routed). */
+int tamd_gemm_routed(const void* A, const void* B, void* C, void* C2, const int32_t* offset, const int32_t* tiles,
+                     int64_t rows_pad, int64_t experts, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                     int64_t ldc, int64_t ldc2, int64_t b_stride, int flags, int epilogue, int dtype, tamd_stream_t stream);
 
 /* ------------------------------------------------------------------ attention (MFMA, flash-style) */
 

@@ -13,7 +13,7 @@ from pathlib import Path
 TAMD_BF16, TAMD_F16, TAMD_F32 = 0, 1, 2
 ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH, ACT_QUICK_GELU, ACT_SILU = 0, 1, 2, 3, 4
 GEMM_A_KM, GEMM_B_KN = 1, 2
-EPI_NONE, EPI_BIAS, EPI_RESIDUAL, EPI_BIAS_ACT, EPI_ACCUM = 0, 1, 2, 3, 4
+EPI_NONE, EPI_BIAS, EPI_RESIDUAL, EPI_BIAS_ACT, EPI_ACCUM, EPI_SWIGLU = 0, 1, 2, 3, 4, 5
 ABI_VERSION = 13
 
 P = c_void_p
@@ -94,6 +94,12 @@ SIGNATURES = {
     "tamd_gemm_colscale": (c_int, [P, P, P, P, I64, I64, I64, I64, I64, I64, c_int, I64, c_float, c_int, P]),
     "tamd_gemm_swiglu": (c_int, [P, P, P, P, I64, I64, I64, I64, I64, I64, I64, c_int, P]),
     "tamd_gemm_swiglu_bwd": (c_int, [P, P, P, P, I64, I64, I64, I64, I64, I64, I64, c_int, P]),
+    "tamd_moe_route_workspace_bytes": (c_size_t, [I64, I64, I64]),
+    "tamd_moe_route": (c_int, [P, P, P, P, P, P, c_size_t, I64, I64, I64, I64, P]),
+    "tamd_moe_gather": (c_int, [P, P, P, P, P, I64, I64, I64, I64, I64, c_int, P]),
+    "tamd_moe_combine": (c_int, [P, P, P, P, I64, I64, I64, c_int, c_int, P]),
+    "tamd_moe_combine_bwd": (c_int, [P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, c_int, c_int, P]),
+    "tamd_gemm_routed": (c_int, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, c_int, c_int, c_int, P]),
     "tamd_dropout_hash": (ctypes.c_uint32, [ctypes.c_uint64, ctypes.c_uint64]),
     "tamd_attn_dropout_field": (ctypes.c_uint32, [ctypes.c_uint64] * 6),
     "tamd_attn_fwd": (c_int, [POINTER(AttnParams), P]),

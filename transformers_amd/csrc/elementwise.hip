@@ -947,3 +947,6 @@ int tamd_cross_entropy_bwd(const void* logits, const int64_t* labels, const floa
 }
 
 }  // extern "C"
+
+// routing of sparse mixture-of-experts blocks (tamd_moe_route / _gather / _combine / _combine_bwd)
+#include "moe_route.inc"

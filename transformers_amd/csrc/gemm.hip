@@ -1937,3 +1937,6 @@ extern "C" int tamd_gemm_swiglu_bwd(const void* dY, const void* Wd, const void* 
 #else
 }  // namespace tamd
 #endif  // TAMD_GEMM_KERNELS_ONLY
+
+// the same body behind a tile table in device memory: the experts of a mixture-of-experts block (tamd_gemm_routed)
+#include "gemm_routed.inc"

@@ -44,7 +44,9 @@ using OptTensor = std::optional<at::Tensor>;
   X(tamd_add) X(tamd_adamw_step) X(tamd_mt_sumsq) X(tamd_mt_norm_finish) X(tamd_mt_scale) X(tamd_mt_adamw_step) X(tamd_sr_bits) X(tamd_sr_round) X(tamd_mt_adamw_step_sr) X(tamd_colsum_workspace_bytes) X(tamd_colsum) X(tamd_transpose)                      \
   X(tamd_cross_entropy_fwd) X(tamd_cross_entropy_bwd) X(tamd_gemm) X(tamd_gemm_workspace_bytes) X(tamd_gemm_ws)       \
   X(tamd_gemm_swiglu) X(tamd_gemm_swiglu_bwd) X(tamd_gemm_colscale) X(tamd_gemm_seg) X(tamd_gemm_group_workspace_bytes) X(tamd_gemm_group) X(tamd_attn_fwd) X(tamd_attn_bwd)   \
-  X(tamd_attn_decode_workspace_bytes) X(tamd_attn_decode)
+  X(tamd_attn_decode_workspace_bytes) X(tamd_attn_decode)                                                            \
+  X(tamd_moe_route_workspace_bytes) X(tamd_moe_route) X(tamd_moe_gather) X(tamd_moe_combine) X(tamd_moe_combine_bwd) \
+  X(tamd_gemm_routed)
 
 struct Api {
   void* handle = nullptr;
@@ -824,6 +826,237 @@ Tensor k_gemm_swiglu_bwd(const Tensor& dy, const Tensor& wd, const Tensor& gu) {
                                    2 * inter, code_of(dy), L.stream),
         "tamd_gemm_swiglu_bwd");
   return dgu;
+}
+
+// ------------------------------------------------------------------------------------------------ sparse MoE experts
+// The experts module of a gated SiLU mixture-of-experts block (MixtralExperts.forward, models/mixtral/modeling_mixtral.py;
+// integrations/moe.py) on expert-sorted buffers: tamd_moe_route / _gather / _combine / _combine_bwd + tamd_gemm_routed.
+// Nothing here reads device data on the host: every size is a function of (tokens, top_k, experts).
+int64_t moe_rows_pad(int64_t pairs, int64_t experts) { return (pairs + 63 * experts + 63) / 64 * 64; }
+int64_t moe_tile_ints(int64_t rows_pad, int64_t experts) { return experts + 1 + (rows_pad + 192 * experts + 255) / 256; }
+Tensor i32_like(const Tensor& x, int64_t n) { return at::empty({n}, x.options().dtype(at::kInt)); }
+
+void k_moe_route(const Tensor& idx, int64_t experts, Tensor& count, Tensor& offset, Tensor& pos, Tensor& tiles) {
+  Launch L({&idx, &count, &offset, &pos, &tiles});
+  TORCH_CHECK(idx.dim() == 2 && idx.scalar_type() == at::kLong && idx.is_contiguous(), "tamd: moe_route takes a contiguous int64 [tokens, top_k] index");
+  const int64_t t = idx.size(0), k = idx.size(1), rows = moe_rows_pad(t * k, experts);
+  TORCH_CHECK(experts >= 1 && experts <= 256, "tamd: moe_route takes 1 .. 256 experts");
+  TORCH_CHECK(count.scalar_type() == at::kInt && offset.scalar_type() == at::kInt && pos.scalar_type() == at::kInt &&
+                  tiles.scalar_type() == at::kInt && count.numel() == experts && offset.numel() == experts + 1 &&
+                  pos.numel() == t * k && tiles.numel() == moe_tile_ints(rows, experts) && count.is_contiguous() &&
+                  offset.is_contiguous() && pos.is_contiguous() && tiles.is_contiguous(),
+              "tamd: moe_route outputs are contiguous int32 [E], [E + 1], [tokens, top_k] and the tile table");
+  const size_t nbytes = api().tamd_moe_route_workspace_bytes(t, k, experts);
+  Tensor ws = at::empty({(int64_t)nbytes}, idx.options().dtype(at::kByte));
+  check(api().tamd_moe_route((const int64_t*)ptr(idx), (int32_t*)mptr(count), (int32_t*)mptr(offset), (int32_t*)mptr(pos),
+                             (int32_t*)mptr(tiles), mptr(ws), nbytes, t, k, experts, rows, L.stream),
+        "tamd_moe_route");
+}
+
+void k_moe_gather(Tensor& xs, const Tensor& x, const Tensor& pos, const Tensor& count, const Tensor& offset) {
+  Launch L({&xs, &x, &pos, &count, &offset});
+  TORCH_CHECK(x.dim() == 2 && x.is_contiguous() && xs.dim() == 2 && xs.is_contiguous() && xs.size(1) == x.size(1) &&
+                  xs.scalar_type() == x.scalar_type() && pos.dim() == 2 && pos.size(0) == x.size(0) && pos.is_contiguous() &&
+                  pos.scalar_type() == at::kInt && count.scalar_type() == at::kInt && offset.scalar_type() == at::kInt &&
+                  offset.numel() == count.numel() + 1,
+              "tamd: moe_gather takes x [tokens, H], pos [tokens, top_k] and xs [rows_pad, H]");
+  check(api().tamd_moe_gather(ptr(x), (const int32_t*)ptr(pos), (const int32_t*)ptr(count), (const int32_t*)ptr(offset),
+                              mptr(xs), x.size(0), pos.size(1), count.numel(), x.size(1), xs.size(0), code_of(x), L.stream),
+        "tamd_moe_gather");
+}
+
+void k_moe_combine(Tensor& out, const Tensor& ys, const Tensor& pos, const OptTensor& w) {
+  Launch L({&out, &ys, &pos, p(w)});
+  TORCH_CHECK(ys.dim() == 2 && ys.is_contiguous() && out.dim() == 2 && out.is_contiguous() && out.size(1) == ys.size(1) &&
+                  out.scalar_type() == ys.scalar_type() && pos.dim() == 2 && pos.size(0) == out.size(0) &&
+                  pos.is_contiguous() && pos.scalar_type() == at::kInt,
+              "tamd: moe_combine takes ys [rows_pad, H], pos [tokens, top_k] and out [tokens, H]");
+  if (w.has_value()) {
+    TORCH_CHECK(w->sizes() == pos.sizes() && w->is_contiguous(), "tamd: moe_combine weights are a contiguous [tokens, top_k]");
+  }
+  check(api().tamd_moe_combine(ptr(ys), (const int32_t*)ptr(pos), ptr(w), mptr(out), out.size(0), pos.size(1), ys.size(1),
+                               w.has_value() ? code_of(*w) : TAMD_F32, code_of(ys), L.stream),
+        "tamd_moe_combine");
+}
+
+void k_moe_combine_bwd(Tensor& dys, Tensor& dw, const Tensor& dout, const Tensor& ys, const Tensor& pos, const Tensor& w,
+                       const Tensor& count, const Tensor& offset) {
+  Launch L({&dys, &dw, &dout, &ys, &pos, &w, &count, &offset});
+  TORCH_CHECK(ys.dim() == 2 && ys.is_contiguous() && dys.sizes() == ys.sizes() && dys.is_contiguous() &&
+                  dys.scalar_type() == ys.scalar_type() && dout.dim() == 2 && dout.is_contiguous() &&
+                  dout.size(1) == ys.size(1) && dout.scalar_type() == ys.scalar_type() && pos.dim() == 2 &&
+                  pos.size(0) == dout.size(0) && pos.is_contiguous() && pos.scalar_type() == at::kInt &&
+                  w.sizes() == pos.sizes() && w.is_contiguous() && dw.sizes() == pos.sizes() && dw.is_contiguous() &&
+                  dw.scalar_type() == w.scalar_type() && count.scalar_type() == at::kInt &&
+                  offset.scalar_type() == at::kInt && offset.numel() == count.numel() + 1,
+              "tamd: moe_combine_bwd takes dout [tokens, H], ys / dys [rows_pad, H], pos / w / dw [tokens, top_k]");
+  check(api().tamd_moe_combine_bwd(ptr(dout), ptr(ys), (const int32_t*)ptr(pos), ptr(w), (const int32_t*)ptr(count),
+                                   (const int32_t*)ptr(offset), mptr(dys), mptr(dw), dout.size(0), pos.size(1), count.numel(),
+                                   ys.size(1), ys.size(0), code_of(w), code_of(ys), L.stream),
+        "tamd_moe_combine_bwd");
+}
+
+// mode 0: c[seg_e] = a[seg_e] . b[e]^T (b [E, N, K]);  1: c[seg_e] = a[seg_e] . b[e] (b [E, K, N]: dX);
+//      2: the SwiGLU way out (b [E, 2I, K]; c = gate|up [rows, 2I] or undefined, c2 = act [rows, I]);
+//      3: c[e] = a[seg_e]^T . b[seg_e] (the weight gradients; c [E, M, N])
+// a, b (mode 3), c, c2: row-major matrices whose row stride may exceed their width (zero-padded K of odd intermediate sizes)
+void k_gemm_routed(Tensor& c, const Tensor& c2, const Tensor& a, const Tensor& b, const Tensor& offset, const Tensor& tiles,
+                   int64_t mode) {
+  Launch L({&c, &c2, &a, &b, &offset, &tiles});
+  TORCH_CHECK(mode >= 0 && mode <= 3, "tamd: gemm_routed mode 0 .. 3");
+  TORCH_CHECK(a.dim() == 2 && a.stride(1) == 1 && offset.scalar_type() == at::kInt && tiles.scalar_type() == at::kInt &&
+                  offset.is_contiguous() && tiles.is_contiguous() && b.scalar_type() == a.scalar_type(),
+              "tamd: gemm_routed takes a row-major A and the int32 plan of moe_route");
+  const int64_t rows = a.size(0), experts = offset.numel() - 1;
+  TORCH_CHECK(tiles.numel() == moe_tile_ints(rows, experts), "tamd: gemm_routed: the tile table does not belong to ", rows, " rows");
+  int64_t M = 0, N, K = 0, ldb, bstride = 0, ldc2 = 0;
+  int flags = 0, epi = TAMD_EPI_NONE;
+  if (mode == 3) {
+    TORCH_CHECK(b.dim() == 2 && b.stride(1) == 1 && b.size(0) == rows && c.defined() && c.dim() == 3 && c.is_contiguous() &&
+                    c.size(0) == experts && c.size(1) == a.size(1) && c.size(2) == b.size(1) &&
+                    c.scalar_type() == a.scalar_type(),
+                "tamd: gemm_routed (weight gradients) takes a [rows, M], b [rows, N], c [E, M, N]");
+    M = a.size(1), N = b.size(1), ldb = b.stride(0);
+    flags = TAMD_GEMM_A_KM | TAMD_GEMM_B_KN;
+    check(api().tamd_gemm_routed(ptr(a), ptr(b), mptr(c), nullptr, (const int32_t*)ptr(offset), (const int32_t*)ptr(tiles), rows,
+                                 experts, M, N, 0, a.stride(0), ldb, N, 0, 0, flags, epi, code_of(a), L.stream),
+          "tamd_gemm_routed");
+    return;
+  }
+  TORCH_CHECK(b.dim() == 3 && b.stride(2) == 1 && b.size(0) == experts && b.stride(1) >= b.size(2),
+              "tamd: gemm_routed takes one row-major weight per expert");
+  K = a.size(1);
+  N = mode == 1 ? b.size(2) : b.size(1);
+  TORCH_CHECK((mode == 1 ? b.size(1) : b.size(2)) == K, "tamd: gemm_routed: K of a and b differ");
+  ldb = b.stride(1), bstride = b.stride(0);
+  if (mode == 1) flags = TAMD_GEMM_B_KN;
+  if (mode == 2) {
+    epi = TAMD_EPI_SWIGLU;
+    TORCH_CHECK(c2.defined() && c2.dim() == 2 && c2.stride(1) == 1 && c2.size(0) == rows && c2.size(1) == N / 2 &&
+                    c2.scalar_type() == a.scalar_type(),
+                "tamd: gemm_routed (SwiGLU) takes act [rows, I]");
+    ldc2 = c2.stride(0);
+  }
+  if (c.defined()) {
+    TORCH_CHECK(c.dim() == 2 && c.stride(1) == 1 && c.size(0) == rows && c.size(1) == N && c.scalar_type() == a.scalar_type(),
+                "tamd: gemm_routed takes c [rows, N]");
+  } else {
+    TORCH_CHECK(mode == 2, "tamd: gemm_routed needs an output");
+  }
+  check(api().tamd_gemm_routed(ptr(a), ptr(b), mptr(c), mode == 2 ? mptr(c2) : nullptr, (const int32_t*)ptr(offset),
+                               (const int32_t*)ptr(tiles), rows, experts, 0, N, K, a.stride(0), ldb, c.defined() ? c.stride(0) : 0,
+                               ldc2, bstride, flags, epi, code_of(a), L.stream),
+        "tamd_gemm_routed");
+}
+
+// a [rows, cols] matrix whose row stride is `ld` >= cols: dense when ld == cols, else a view of a zero-filled [rows, ld] one
+// (the zero columns extend K to whole 64-deep stages: intermediate sizes that are not multiples of 64)
+Tensor moe_matrix(const Tensor& like, int64_t rows, int64_t cols, int64_t ld) {
+  if (ld == cols) return at::empty({rows, cols}, like.options());
+  return at::zeros({rows, ld}, like.options()).narrow(1, 0, cols);
+}
+// w [E, r, c] with its rows (dim 1) or columns (dim 2) zero-padded to `n`
+Tensor moe_pad_weight(const Tensor& w, int64_t dim, int64_t n) {
+  if (w.size(dim) == n) return w;
+  auto shape = w.sizes().vec();
+  shape[(size_t)dim] = n;
+  Tensor out = at::zeros(shape, w.options());
+  out.narrow(dim, 0, w.size(dim)).copy_(w);
+  return out;
+}
+int64_t up64(int64_t v) { return (v + 63) / 64 * 64; }
+
+// -> (out [T, H], pos, count, offset, tiles, xs [rows, H], gus [rows, 2I], acts [rows, I], ys [rows, H]); gus is empty when
+// nothing will be differentiated
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> op_moe_experts(
+    const Tensor& x, const Tensor& top_k_index, const Tensor& top_k_weights, const Tensor& gate_up, const Tensor& down, bool train) {
+  TORCH_CHECK(x.dim() == 2 && gate_up.dim() == 3 && down.dim() == 3 && top_k_index.dim() == 2 && top_k_index.size(0) == x.size(0) &&
+                  top_k_weights.sizes() == top_k_index.sizes(),
+              "tamd: moe_experts takes x [T, H], top_k_index / top_k_weights [T, k], gate_up [E, 2I, H], down [E, H, I]");
+  const int64_t t = x.size(0), h = x.size(1), k = top_k_index.size(1), e = gate_up.size(0), inter = down.size(2);
+  TORCH_CHECK(gate_up.size(1) == 2 * inter && gate_up.size(2) == h && down.size(0) == e && down.size(1) == h &&
+                  gate_up.scalar_type() == x.scalar_type() && down.scalar_type() == x.scalar_type(),
+              "tamd: moe_experts: gate_up [E, 2I, H] and down [E, H, I] do not match x");
+  TORCH_CHECK(h % 64 == 0 && inter % 8 == 0 && e <= 256, "tamd: moe_experts takes H % 64 == 0, I % 8 == 0, E <= 256");
+  const Tensor xc = contig(x), idx = contig(top_k_index), w = contig(top_k_weights), wgu = contig(gate_up), wd = contig(down);
+  const int64_t rows = moe_rows_pad(t * k, e);
+  Tensor count = i32_like(x, e), offset = i32_like(x, e + 1), pos = at::empty({t, k}, x.options().dtype(at::kInt)),
+         tiles = i32_like(x, moe_tile_ints(rows, e));
+  k_moe_route(idx, e, count, offset, pos, tiles);
+  Tensor xs = at::empty({rows, h}, x.options());
+  k_moe_gather(xs, xc, pos, count, offset);
+  Tensor gus = train ? moe_matrix(x, rows, 2 * inter, up64(2 * inter)) : Tensor();
+  Tensor acts = moe_matrix(x, rows, inter, up64(inter));
+  k_gemm_routed(gus, acts, xs, wgu, offset, tiles, 2);
+  Tensor ys = at::empty({rows, h}, x.options());
+  if (inter % 64 == 0) {
+    k_gemm_routed(ys, Tensor(), acts, wd, offset, tiles, 0);
+  } else {  // K = I extended to whole stages by zero columns on both sides
+    const Tensor acts_k = acts.as_strided({rows, up64(inter)}, {up64(inter), 1}, acts.storage_offset());
+    k_gemm_routed(ys, Tensor(), acts_k, moe_pad_weight(wd, 2, up64(inter)), offset, tiles, 0);
+  }
+  Tensor out = at::empty({t, h}, x.options());
+  k_moe_combine(out, ys, pos, w);
+  return {out, pos, count, offset, tiles, xs, train ? gus : nothing(x), acts, ys};
+}
+
+// -> (dx [T, H], d top_k_weights [T, k], d gate_up [E, 2I, H], d down [E, H, I])
+std::tuple<Tensor, Tensor, Tensor, Tensor> op_moe_experts_bwd(const Tensor& dout, const Tensor& top_k_weights, const Tensor& gate_up,
+                                                              const Tensor& down, const Tensor& pos, const Tensor& count,
+                                                              const Tensor& offset, const Tensor& tiles, const Tensor& xs,
+                                                              const Tensor& gus, const Tensor& acts, const Tensor& ys) {
+  TORCH_CHECK(gus.numel() > 0, "tamd: moe_experts was run with train=False but is being differentiated");
+  const int64_t t = pos.size(0), h = xs.size(1), e = gate_up.size(0), inter = down.size(2), rows = xs.size(0);
+  const Tensor w = contig(top_k_weights), wgu = contig(gate_up), wd = contig(down), g = contig(dout);
+  // 1. the combine: d ys and d top_k_weights
+  Tensor dys = at::empty({rows, h}, xs.options()), dw = at::empty_like(w);
+  k_moe_combine_bwd(dys, dw, g, ys, pos, w, count, offset);
+  // 2. d act = d ys . down   (per expert; down_proj[e] [H, I] is the k-major B operand)
+  Tensor dacts = at::empty({rows, inter}, xs.options());
+  k_gemm_routed(dacts, Tensor(), dys, wd, offset, tiles, 1);
+  // 3. the SiLU*up backward on the sorted buffer (gus keeps its forward row stride)
+  const int64_t ldgu = gus.stride(0), esz = gus.element_size();
+  Tensor dgus = moe_matrix(xs, rows, 2 * inter, ldgu);
+  {
+    Launch L({&gus, &dacts, &dgus});
+    check(api().tamd_swiglu_bwd(ptr(gus), (const char*)ptr(gus) + inter * esz, ptr(dacts), mptr(dgus),
+                                (char*)mptr(dgus) + inter * esz, nullptr, rows, inter, ldgu, inter, code_of(gus), L.stream),
+          "tamd_swiglu_bwd");
+  }
+  // 4. d xs = d gus . gate_up   (K = 2I, extended to whole stages by zero columns / zero weight rows when 2I % 64 != 0)
+  Tensor dxs = at::empty({rows, h}, xs.options());
+  if (ldgu == 2 * inter) {
+    k_gemm_routed(dxs, Tensor(), dgus, wgu, offset, tiles, 1);
+  } else {
+    const Tensor dgus_k = dgus.as_strided({rows, ldgu}, {ldgu, 1}, dgus.storage_offset());
+    k_gemm_routed(dxs, Tensor(), dgus_k, moe_pad_weight(wgu, 1, ldgu), offset, tiles, 1);
+  }
+  // 5. the gather's gradient: the combine with unit weights
+  Tensor dx = at::empty({t, h}, xs.options());
+  k_moe_combine(dx, dxs, pos, {});
+  // 6. the weight gradients, K routed: d down[e] = d ys_e^T . act_e, d gate_up[e] = d gus_e^T . xs_e
+  Tensor ddown = at::empty({e, h, inter}, xs.options()), dgate_up = at::empty({e, 2 * inter, h}, xs.options());
+  k_gemm_routed(ddown, Tensor(), dys, acts, offset, tiles, 3);
+  k_gemm_routed(dgate_up, Tensor(), dgus, xs, offset, tiles, 3);
+  return {dx, dw, dgate_up, ddown};
+}
+
+// kernel-level ops (tests, tools): outputs are the caller's buffers
+void op_moe_route_out(Tensor& count, Tensor& offset, Tensor& pos, Tensor& tiles, const Tensor& idx, int64_t experts) {
+  k_moe_route(idx, experts, count, offset, pos, tiles);
+}
+void op_moe_gather_out(Tensor& xs, const Tensor& x, const Tensor& pos, const Tensor& count, const Tensor& offset) {
+  k_moe_gather(xs, x, pos, count, offset);
+}
+void op_moe_combine_out(Tensor& out, const Tensor& ys, const Tensor& pos, const OptTensor& w) { k_moe_combine(out, ys, pos, w); }
+void op_moe_combine_bwd_out(Tensor& dys, Tensor& dw, const Tensor& dout, const Tensor& ys, const Tensor& pos, const Tensor& w,
+                            const Tensor& count, const Tensor& offset) {
+  k_moe_combine_bwd(dys, dw, dout, ys, pos, w, count, offset);
+}
+void op_gemm_routed_out(Tensor& c, const OptTensor& c2, const Tensor& a, const Tensor& b, const Tensor& offset, const Tensor& tiles,
+                        int64_t mode, bool need_c) {
+  Tensor none;
+  k_gemm_routed(need_c ? c : none, c2.has_value() ? *c2 : Tensor(), a, b, offset, tiles, mode);
 }
 
 // Which of the two bit-identical forms of the SiLU*up backward runs -- the dX GEMM's way out (tamd_gemm_swiglu_bwd) or GEMM +
@@ -1667,6 +1900,15 @@ TORCH_LIBRARY(tamd, m) {
   m.def("rope(Tensor x, Tensor cos, Tensor sin, int nheads, int head_dim, bool conj=False) -> Tensor");
   m.def("attention(Tensor q, Tensor k, Tensor v, Tensor? key_valid, float scale, bool causal, float dropout_p, int seed, "
         "Tensor? q_start, bool train, Tensor? seed_dev=None, Tensor? kv_len=None) -> (Tensor, Tensor)");
+  m.def("moe_route_out(Tensor(a!) count, Tensor(b!) offset, Tensor(c!) pos, Tensor(d!) tiles, Tensor top_k_index, int experts) -> ()");
+  m.def("moe_gather_out(Tensor(a!) xs, Tensor x, Tensor pos, Tensor count, Tensor offset) -> ()");
+  m.def("moe_combine_out(Tensor(a!) out, Tensor ys, Tensor pos, Tensor? w) -> ()");
+  m.def("moe_combine_bwd_out(Tensor(a!) dys, Tensor(b!) dw, Tensor dout, Tensor ys, Tensor pos, Tensor w, Tensor count, Tensor offset) -> ()");
+  m.def("gemm_routed_out(Tensor(a!) c, Tensor(b!)? c2, Tensor a, Tensor b, Tensor offset, Tensor tiles, int mode, bool need_c=True) -> ()");
+  m.def("moe_experts(Tensor x, Tensor top_k_index, Tensor top_k_weights, Tensor gate_up, Tensor down, bool train) -> "
+        "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("moe_experts_bwd(Tensor dout, Tensor top_k_weights, Tensor gate_up, Tensor down, Tensor pos, Tensor count, Tensor offset, "
+        "Tensor tiles, Tensor xs, Tensor gus, Tensor acts, Tensor ys) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("swiglu(Tensor gu) -> Tensor");
   m.def("bias_act(Tensor x, Tensor? bias, int act) -> Tensor");
   m.def("embedding(Tensor ids, Tensor table, int padding_idx=-1) -> Tensor");
@@ -1735,6 +1977,13 @@ TORCH_LIBRARY(tamd, m) {
   m.impl("sr_round_bf16", &k_sr_round_bf16);                         \
   m.impl("gemm", &op_gemm);                                          \
   m.impl("gemm_out", &op_gemm_out);                                  \
+  m.impl("moe_route_out", &op_moe_route_out);                        \
+  m.impl("moe_gather_out", &op_moe_gather_out);                      \
+  m.impl("moe_combine_out", &op_moe_combine_out);                    \
+  m.impl("moe_combine_bwd_out", &op_moe_combine_bwd_out);            \
+  m.impl("gemm_routed_out", &op_gemm_routed_out);                    \
+  m.impl("moe_experts", &op_moe_experts);                            \
+  m.impl("moe_experts_bwd", &op_moe_experts_bwd);                    \
   m.impl("gemm_swiglu", &op_gemm_swiglu);                            \
   m.impl("gemm_swiglu_bwd", &k_gemm_swiglu_bwd);                     \
   m.impl("attn_fwd", &op_attn_fwd);                                  \

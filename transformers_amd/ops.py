@@ -320,6 +320,74 @@ def raw_attn_bwd(q, k, v, o, lse, dout, scale, causal, key_valid=None, dq=None, 
     return dq, dk, dv
 
 
+# ---- sparse mixture-of-experts (include/tamd.h: tamd_moe_* and tamd_gemm_routed) ----------------------------------------
+def moe_rows_pad(pairs: int, experts: int) -> int:
+    """Rows of the expert-sorted buffers: every expert's segment is padded to a multiple of 64 rows, so S + 63 E rounded
+    up to 64 always holds them -- a function of the shapes alone."""
+    return (pairs + 63 * experts + 63) // 64 * 64
+
+
+def moe_tile_ints(rows_pad: int, experts: int) -> int:
+    """int32 words of the tile table `raw_moe_route` writes for `raw_gemm_routed` (include/tamd.h tamd_moe_route)."""
+    return experts + 1 + (rows_pad + 192 * experts + 255) // 256
+
+
+def raw_moe_route(top_k_index, experts):
+    """top_k_index int64 [T, k] -> (count [E], offset [E + 1], pos [T, k], tiles), all int32 on the index's device."""
+    t, k = top_k_index.shape
+    i32 = dict(dtype=torch.int32, device=top_k_index.device)
+    count, offset, pos = torch.empty(experts, **i32), torch.empty(experts + 1, **i32), torch.empty(t, k, **i32)
+    tiles = torch.empty(moe_tile_ints(moe_rows_pad(t * k, experts), experts), **i32)
+    T.moe_route_out(count, offset, pos, tiles, top_k_index, int(experts))
+    return count, offset, pos, tiles
+
+
+def raw_moe_gather(x, pos, count, offset, out=None):
+    """xs[pos[t, j]] = x[t]; rows of xs [rows_pad, H] that no pair owns are zeros."""
+    xs = out if out is not None else x.new_empty(moe_rows_pad(pos.numel(), count.numel()), x.shape[1])
+    T.moe_gather_out(xs, x, pos, count, offset)
+    return xs
+
+
+def raw_moe_combine(ys, pos, w=None, out=None):
+    """out[t] = round(sum_j w[t, j] * ys[pos[t, j]]) (fp32 products and sum, one rounding); w None: unit weights."""
+    o = out if out is not None else ys.new_empty(pos.shape[0], ys.shape[1])
+    T.moe_combine_out(o, ys, pos, w)
+    return o
+
+
+def raw_moe_combine_bwd(dout, ys, pos, w, count, offset, dys=None, dw=None):
+    """-> (dys [rows_pad, H] with zero padding rows, dw [T, k] in w's dtype)."""
+    dys = dys if dys is not None else torch.empty_like(ys)
+    dw = dw if dw is not None else torch.empty_like(w)
+    T.moe_combine_bwd_out(dys, dw, dout, ys, pos, w, count, offset)
+    return dys, dw
+
+
+ROUTED_NT, ROUTED_NN, ROUTED_SWIGLU, ROUTED_DW = 0, 1, 2, 3
+
+
+def raw_gemm_routed(a, b, offset, tiles, mode=ROUTED_NT, out=None, out2=None, need_gu=True):
+    """The experts' products over the plan of `raw_moe_route` in one launch (include/tamd.h tamd_gemm_routed).
+    ROUTED_NT: c[seg_e] = a[seg_e] . b[e]^T (b [E, N, K]);  ROUTED_NN: c[seg_e] = a[seg_e] . b[e] (b [E, K, N], the dX layout);
+    ROUTED_SWIGLU: b [E, 2I, K] -> (gate|up [rows, 2I] or None, act [rows, I]);  ROUTED_DW: a [rows, M], b [rows, N] ->
+    c [E, M, N] = a[seg_e]^T . b[seg_e] (zeros for an expert without rows)."""
+    rows = a.shape[0]
+    if mode == ROUTED_DW:
+        c = out if out is not None else a.new_empty(offset.numel() - 1, a.shape[1], b.shape[1])
+        T.gemm_routed_out(c, None, a, b, offset, tiles, mode, True)
+        return c
+    n = b.shape[2] if mode == ROUTED_NN else b.shape[1]
+    if mode == ROUTED_SWIGLU:
+        act = out2 if out2 is not None else a.new_empty(rows, n // 2)
+        gu = out if out is not None else (a.new_empty(rows, n) if need_gu else None)
+        T.gemm_routed_out(gu if gu is not None else act, act, a, b, offset, tiles, mode, gu is not None)
+        return gu, act
+    c = out if out is not None else a.new_empty(rows, n)
+    T.gemm_routed_out(c, None, a, b, offset, tiles, mode, True)
+    return c
+
+
 # --------------------------------------------------------------------------- fake (Meta) implementations + autograd
 # The ops are defined and implemented in csrc/torch_binding.cpp; what Python adds per op is its fake implementation
 # (shapes without data: tracing / shape tooling / opcheck) and, for the differentiable ones, the autograd formula --
@@ -399,6 +467,11 @@ register("mt_adamw_step_sr_", lambda table, n_tensors, total_chunks, lr, beta1, 
 register("sr_round_bf16", lambda x, key, step: torch.empty_like(x, dtype=torch.bfloat16,
                                                                 memory_format=torch.contiguous_format))
 
+register("moe_route_out", lambda count, offset, pos, tiles, top_k_index, experts: None)
+register("moe_gather_out", lambda xs, x, pos, count, offset: None)
+register("moe_combine_out", lambda out, ys, pos, w: None)
+register("moe_combine_bwd_out", lambda dys, dw, dout, ys, pos, w, count, offset: None)
+register("gemm_routed_out", lambda c, c2, a, b, offset, tiles, mode, need_c=True: None)
 
 def _gemm_shape(a, b, a_km, b_kn):
     return (a.shape[1] if a_km else a.shape[0]), (b.shape[1] if b_kn else b.shape[0])
@@ -662,6 +735,43 @@ register("swiglu", lambda gu: gu.new_empty(*gu.shape[:-1], gu.shape[-1] // 2), _
          lambda ctx, inputs, output: ctx.save_for_backward(inputs[0]))
 
 
+# The experts of a gated SiLU mixture-of-experts block (MixtralExperts.forward, models/mixtral/modeling_mixtral.py, behind
+# integrations/moe.py's ExpertsInterface): route, gather, gate|up product with the SiLU*up way out, down product, combine --
+# and the backward through the same plan (csrc/torch_binding.cpp op_moe_experts / op_moe_experts_bwd).
+def _moe_experts_fake(x, top_k_index, top_k_weights, gate_up, down, train):
+    t, k = top_k_index.shape
+    e, inter, h = gate_up.shape[0], down.shape[2], x.shape[1]
+    rows = moe_rows_pad(t * k, e)
+    i32 = lambda *shape: x.new_empty(shape, dtype=torch.int32)  # noqa: E731
+    return (x.new_empty(t, h), i32(t, k), i32(e), i32(e + 1), i32(moe_tile_ints(rows, e)), x.new_empty(rows, h),
+            x.new_empty(rows, 2 * inter) if train else _nothing(x), x.new_empty(rows, inter), x.new_empty(rows, h))
+
+
+def _moe_experts_bwd_fake(dout, top_k_weights, gate_up, down, pos, count, offset, tiles, xs, gus, acts, ys):
+    return (dout.new_empty(pos.shape[0], xs.shape[1]), torch.empty_like(top_k_weights, memory_format=torch.contiguous_format),
+            torch.empty_like(gate_up, memory_format=torch.contiguous_format),
+            torch.empty_like(down, memory_format=torch.contiguous_format))
+
+
+def _moe_experts_setup(ctx, inputs, output):
+    _x, _idx, w, gate_up, down, _train = inputs
+    _out, pos, count, offset, tiles, xs, gus, acts, ys = output
+    ctx.save_for_backward(w, gate_up, down, pos, count, offset, tiles, xs, gus, acts, ys)
+    ctx.set_materialize_grads(False)
+
+
+def _moe_experts_backward(ctx, dout, *_aux):
+    w, gate_up, down, pos, count, offset, tiles, xs, gus, acts, ys = ctx.saved_tensors
+    if gus.numel() == 0:
+        raise TamdError("moe_experts was run with train=False but is being differentiated")
+    dx, dw, dgate_up, ddown = T.moe_experts_bwd(dout, w, gate_up, down, pos, count, offset, tiles, xs, gus, acts, ys)
+    return dx, None, dw, dgate_up, ddown, None
+
+
+register("moe_experts_bwd", _moe_experts_bwd_fake)
+register("moe_experts", _moe_experts_fake, _moe_experts_backward, _moe_experts_setup)
+
+
 def _bias_act_setup(ctx, inputs, output):
     ctx.save_for_backward(inputs[0], inputs[1])
     ctx.act = inputs[2]
@@ -908,6 +1018,13 @@ def linear_swiglu(x2, wgu):
     """Inference only: SiLU(x2 . Wg^T) * (x2 . Wu^T) for wgu = [Wg ; Wu] from ONE product (`gemm_swiglu_supported` shapes: the
     GEMM epilogue, or the weight-streaming kernel at M <= 16), gate | up themselves not kept."""
     return T.gemm_swiglu(x2, wgu, False)[1]
+
+
+def moe_experts(x, top_k_index, top_k_weights, gate_up_proj, down_proj):
+    """The experts module of a gated SiLU mixture-of-experts block: x [T, H], top_k_index int64 [T, k], top_k_weights [T, k]
+    (fp32 or x's dtype), gate_up_proj [E, 2I, H] = [gate ; up] rows per expert, down_proj [E, H, I]  ->  [T, H]."""
+    train = _wants_grad(x, top_k_weights, gate_up_proj, down_proj)
+    return T.moe_experts(x, top_k_index, top_k_weights, gate_up_proj, down_proj, train)[0]
 
 
 def bias_act(x, bias, act):

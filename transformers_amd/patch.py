@@ -13,7 +13,7 @@ from typing import Dict, Type
 import torch
 from torch import nn
 
-from . import attention
+from . import attention, experts
 
 
 def _tables() -> Dict[Type[nn.Module], Type[nn.Module]]:
@@ -26,11 +26,14 @@ def _tables() -> Dict[Type[nn.Module], Type[nn.Module]]:
 
 
 def accelerate(model: nn.Module, attn_implementation: bool = True, fuse_loss: bool = True,
-               fused_lm_head_loss: bool = False) -> nn.Module:
+               fused_lm_head_loss: bool = False, experts_implementation: bool = True) -> nn.Module:
     """Switch `model` (any PreTrainedModel containing Llama / BERT / CLIP / GPT-2 blocks) to the MI355X path.
 
     * registers and selects `attn_implementation="tamd"` (reference API: `set_attn_implementation`,
       src/transformers/modeling_utils.py:2041-2139);
+    * on a sparse mixture-of-experts model (one whose experts sit behind `@use_experts_implementation`) registers and selects
+      `experts_implementation="tamd"` (reference API: `set_experts_implementation`, modeling_utils.py); `revert` restores
+      what `get_experts_implementation()` returned before;
     * swaps norm / MLP / attention / layer modules for their tamd subclasses in place;
     * installs the fused cross-entropy as `model.loss_function` for causal-LM heads
       (reference hook: modeling_utils.py:4652-4669);
@@ -39,6 +42,7 @@ def accelerate(model: nn.Module, attn_implementation: bool = True, fuse_loss: bo
     Returns the same object.
     """
     attention.register()
+    experts.register()
     table = _tables()
     n = 0
     for m in model.modules():
@@ -80,6 +84,13 @@ def accelerate(model: nn.Module, attn_implementation: bool = True, fuse_loss: bo
                           "(the MI355X kernels run bf16/fp16; load with dtype=torch.bfloat16 to use them)")
         else:
             model.set_attn_implementation(attention.ATTN_KEY)
+    can_set = getattr(model, "_can_set_experts_implementation", None)
+    if experts_implementation and callable(can_set) and can_set() and hasattr(model, "set_experts_implementation"):
+        dtypes = {p.dtype for p in model.parameters() if p.is_floating_point()}
+        if not dtypes or dtypes & {torch.bfloat16, torch.float16}:  # (an fp32 model keeps its experts, like its attention)
+            if "_tamd_experts_was" not in model.__dict__:
+                model.__dict__["_tamd_experts_was"] = dict(model.get_experts_implementation())
+            model.set_experts_implementation(experts.EXPERTS_KEY)
     # eager weight fusion (before DDP wraps the model)
     for m in model.modules():
         fuse = getattr(m, "_fused", None)
@@ -132,6 +143,8 @@ def revert(model: nn.Module) -> nn.Module:
     model.__dict__.pop("forward", None)  # the instance-level fused forward, if installed
     if "_tamd_disable_compile_was" in model.__dict__ and getattr(model, "generation_config", None) is not None:
         model.generation_config.disable_compile = model.__dict__.pop("_tamd_disable_compile_was")
+    if "_tamd_experts_was" in model.__dict__:
+        model.set_experts_implementation(model.__dict__.pop("_tamd_experts_was"))
     from . import graph_stack
 
     graph_stack.detach(model)
