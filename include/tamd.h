@@ -458,6 +458,27 @@ int tamd_attn_fwd(const struct tamd_attn_params* p, tamd_stream_t stream);
 size_t tamd_attn_decode_workspace_bytes(const struct tamd_attn_params* p);
 int tamd_attn_decode(const struct tamd_attn_params* p, void* workspace, size_t workspace_bytes, tamd_stream_t stream);
 
+/* (Added under ABI 13: new entry points, tamd_attn_params keeps its layout.)  The same two schedules under a CAUSAL SLIDING
+ * WINDOW over a KV cache -- what `generate` needs from a model whose config has a `sliding_window` (Mistral, Ministral, Phi-3,
+ * the sliding layers of Gemma-3 / Cohere2, Mixtral with a window): sliding_window_overlay AND-ed with causal_mask_function
+ * (masking_utils.py:92-101, :134-138, built by create_sliding_window_causal_mask :1102) over the keys that a
+ * DynamicSlidingWindowLayer / StaticSlidingWindowLayer returns from `update` (cache_utils.py:203-277, :504-628; call sites
+ * models/mistral/modeling_mistral.py:172, :364).  With off = seq_k - seq_q, key k is
+ * visible to query row s iff
+ *     s + off - window + 1 <= k <= s + off        and key_valid (when given) allows it;
+ * with seq_q == 1 that is every key >= seq_k - window, whatever `causal` says.  The lower bound is computed in the kernel
+ * from the row index (no plane is read); key tiles wholly left of a workgroup's first bound are neither loaded nor visited, so
+ * the time follows the window, not the key count; under the split-KV schedule a piece left of the bound leaves as "saw no
+ * key" -- the plan and the workspace stay those of tamd_attn_decode for the same p.  A row without a visible key: O = 0,
+ * lse = +inf.  At seq_q == seq_k the result has the bits of tamd_attn_fwd with the q_start planes of the same window; with
+ * window >= seq_k those of tamd_attn_fwd / tamd_attn_decode.
+ * Inference only (there is no backward).  TAMD_E_ARG for: window < 1; seq_q > seq_k; seq_q > 1 with causal == 0;
+ * q_start != NULL; dropout_p != 0; seq_k_dev != NULL (no reference cache produces a binding window over device-side counts).
+ * Every other check is that of tamd_attn_fwd / tamd_attn_decode. */
+int tamd_attn_fwd_window(const struct tamd_attn_params* p, int64_t window, tamd_stream_t stream);
+int tamd_attn_decode_window(const struct tamd_attn_params* p, int64_t window, void* workspace, size_t workspace_bytes,
+                            tamd_stream_t stream); /* workspace: tamd_attn_decode_workspace_bytes(p) */
+
 /* Backward (SURVEY §8a "Attention"): delta = rowsum(dO*O); dV = P^T dO; dS = P*(dP - delta);
  * dQ = scale dS K; dK = scale dS^T Q; GQA sums dK/dV over the query heads of a group. */
 struct tamd_attn_bwd_params {

@@ -105,6 +105,8 @@ SIGNATURES = {
     "tamd_attn_fwd": (c_int, [POINTER(AttnParams), P]),
     "tamd_attn_decode_workspace_bytes": (c_size_t, [POINTER(AttnParams)]),
     "tamd_attn_decode": (c_int, [POINTER(AttnParams), P, c_size_t, P]),
+    "tamd_attn_fwd_window": (c_int, [POINTER(AttnParams), I64, P]),
+    "tamd_attn_decode_window": (c_int, [POINTER(AttnParams), I64, P, c_size_t, P]),
     "tamd_attn_bwd": (c_int, [POINTER(AttnBwdParams), P]),
 }
 

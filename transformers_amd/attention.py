@@ -26,13 +26,15 @@ class TamdMask:
     """What `tamd_mask` hands to the attention function when a 2-D mask does not say it all: the 2-D key-validity mask (or
     None) plus, for packed sequences, `q_start` (int32 [2, B, S]: first token of every query's sequence, last token of every
     key's sequence) or, for a decode step over a pre-allocated cache, `kv_len` (int32 [B] on the device: the key slots in use,
-    `tamd_attn_params.seq_k_dev` -- the key-validity mask then covers the whole allocation).  The decoder layers pass it
-    along untouched as `attention_mask`."""
+    `tamd_attn_params.seq_k_dev` -- the key-validity mask then covers the whole allocation) or, for a multi-token step over a
+    sliding-window cache whose first rows no longer see the oldest keys they are handed, `window` (int: query i of n sees the
+    keys i + L - n - window + 1 .. i + L - n of the L returned by the cache; the key-validity mask covers exactly those L).  The
+    decoder layers pass it along untouched as `attention_mask`."""
 
-    __slots__ = ("key_valid", "q_start", "kv_len")
+    __slots__ = ("key_valid", "q_start", "kv_len", "window")
 
-    def __init__(self, key_valid, q_start, kv_len=None):
-        self.key_valid, self.q_start, self.kv_len = key_valid, q_start, kv_len
+    def __init__(self, key_valid, q_start, kv_len=None, window=None):
+        self.key_valid, self.q_start, self.kv_len, self.window = key_valid, q_start, kv_len, window
 
     # `generate` with a pre-allocated cache prepares the step's mask BEFORE the forward (generation/utils.py
     # prepare_inputs_for_generation -> create_masks_for_generate), and the forward's own create_causal_mask then receives that
@@ -43,7 +45,7 @@ class TamdMask:
     def to(self, device=None, dtype=None, **_kw):
         move = (lambda t: t if t is None else t.to(device=device))
         kv = self.key_valid if self.key_valid is None else self.key_valid.to(device=device, dtype=dtype)
-        return TamdMask(kv, move(self.q_start), move(self.kv_len))
+        return TamdMask(kv, move(self.q_start), move(self.kv_len), self.window)
 
 
 def _mask_kv_len(attention_mask) -> Optional[int]:
@@ -97,7 +99,9 @@ def tamd_mask(batch_size, q_length, kv_length, q_offset=0, kv_offset=0, mask_fun
     if padding is not None:
         if padding.dim() != 2:
             raise TamdError(f"attn_implementation='tamd' takes a 2-D attention_mask, got {tuple(padding.shape)}")
-        if (short := kv_length + kv_offset - padding.shape[-1]) > 0:
+        if kv_offset != 0 and padding.shape[-1] == kv_length:
+            pass  # this step's mask over a cropped cache, prepared before the forward (see TamdMask): already the window
+        elif (short := kv_length + kv_offset - padding.shape[-1]) > 0:
             padding = torch.nn.functional.pad(padding, (0, short))
         padding = padding[:, kv_offset: kv_offset + kv_length] if padding.shape[-1] != kv_length else padding
     bidirectional = getattr(mu, "bidirectional_mask_function", None)
@@ -106,6 +110,9 @@ def tamd_mask(batch_size, q_length, kv_length, q_offset=0, kv_offset=0, mask_fun
         # kv_length = encoder length != q_length, masking_utils.py:1000-1080): every query sees every valid key; there is
         # no cache geometry to decode
         return padding
+    window = _sliding_cache_window(mask_function, kwargs)
+    if window is not None and (torch.is_tensor(q_offset) or q_offset != 0 or kv_offset != 0 or kv_length != q_length):
+        return _sliding_cache_mask(batch_size, q_length, kv_length, q_offset, kv_offset, window, padding, attention_mask, kwargs)
     kv_len = None
     dynamic = not torch.is_tensor(q_offset) and kv_offset == 0 and kv_length == q_offset + q_length
     if not dynamic:
@@ -173,6 +180,59 @@ def tamd_mask(batch_size, q_length, kv_length, q_offset=0, kv_offset=0, mask_fun
     return padding if bounds is None else TamdMask(padding, bounds)
 
 
+def _sliding_cache_window(mask_function, kwargs) -> Optional[int]:
+    """The window W of a call that `create_sliding_window_causal_mask` makes for a sliding cache layer (masking_utils.py:1102:
+    `sliding_window_causal_mask_function(W)` and, as `local_size`, the size its cache layers crop to), or None: the mask
+    function must decompose into exactly `causal_mask_function` and one or more `sliding_window_overlay` leaves (W: their
+    minimum).  A call that does not say what the cache keeps (no `local_size`) is no such call: an overlay over a cache of
+    unknown kind stays refused below, whatever its geometry."""
+    from transformers import masking_utils as mu
+
+    if mask_function is None or kwargs.get("local_size") is None:
+        return None
+    window = None
+    for leaf in _decompose_mask_function(mask_function):
+        if leaf is mu.causal_mask_function:
+            continue
+        w = _closure_vars(leaf).get("sliding_window") if _overlay_kind(leaf) == "sliding" else None
+        if not isinstance(w, int) or isinstance(w, bool):
+            return None
+        window = w if window is None else min(window, w)
+    return window
+
+
+def _sliding_cache_mask(batch_size, n, length, q_offset, kv_offset, window, padding, attention_mask, kwargs):
+    """The mask of a forward over a sliding-window cache layer (DynamicSlidingWindowLayer / StaticSlidingWindowLayer,
+    cache_utils.py:203-277, :504-628).  Query i stands at P + i, key j of the `length` keys the layer returns at o + j; the
+    reference's mask is o + j <= P + i and o + j > P + i - W.  Two geometries occur: ALIGNED (o + L == P + n: the layer returns
+    the concatenation of what it kept and the new keys -- the kernels' bottom-right diagonal) and the STATIC PREFIX (o == 0,
+    L the allocation, slots 0 .. P + n - 1 in use, only while P + n <= W).  The window binds iff o <= P + n - 1 - W."""
+    from transformers import masking_utils as mu
+
+    if torch.is_tensor(q_offset):
+        raise TamdError("attn_implementation='tamd': a sliding-window mask over a cache whose query offset is a device tensor "
+                        "(a non-sliding StaticLayer under a sliding-window mask) is not supported; use 'sdpa' or 'eager'")
+    p, o = int(q_offset), int(kv_offset)
+    aligned = o + length == p + n
+    binds = o <= p + n - 1 - window
+    if not binds:
+        if o == 0:  # the dynamic aligned form and the static prefix: what the plain causal mask gives for this geometry
+            return tamd_mask(batch_size, n, length, q_offset=q_offset, kv_offset=0, mask_function=mu.causal_mask_function,
+                             attention_mask=attention_mask, **kwargs)
+        if aligned:  # a cropped cache: every key it hands out is inside every query's window; the diagonal is bottom-right
+            return padding
+        raise TamdError(f"attn_implementation='tamd': {n} queries at offset {p} over {length} keys at offset {o} are not the "
+                        "keys a sliding-window cache returns (kv_offset + kv_length != q_offset + q_length); use 'sdpa' or 'eager'")
+    if n == 1:
+        raise TamdError("attn_implementation='tamd': one query over a cache that keeps keys its sliding window has left behind "
+                        f"(window {window}, {length} keys from offset {o}, query at {p}) -- a cache that does not crop to the "
+                        "window; use a sliding-window cache (DynamicCache(config=...) / StaticCache(config=...)) or 'sdpa' / 'eager'")
+    if not aligned:
+        raise TamdError(f"attn_implementation='tamd': a binding sliding window (window {window}) over {length} keys at offset "
+                        f"{o} that do not end at the last query ({n} queries at offset {p}); use 'sdpa' or 'eager'")
+    return TamdMask(padding, None, None, window)
+
+
 def _overlay_kind(leaf) -> Optional[str]:
     """Which of the reference's mask overlays a leaf of the `and_masks` tree is, by the factory that made it
     (masking_utils.py:92-101 sliding_window_overlay, :104-113 chunked_overlay, :182-190 packed_sequence_mask_function)."""
@@ -198,6 +258,9 @@ def _refuse_kv_len(attention_mask) -> None:
     if isinstance(attention_mask, TamdMask) and attention_mask.kv_len is not None:
         raise TamdError("a decode-step mask (key counts in device memory) reached a fused block that does not implement it "
                         "(supported: the registered attention function and the cached Llama path)")
+    if isinstance(attention_mask, TamdMask) and attention_mask.window is not None:
+        raise TamdError("a sliding-window step over a KV cache reached a fused block that does not implement it (supported: "
+                        "the registered attention function)")
 
 
 def split_mask(attention_mask, batch: int, kv_len: int):
@@ -360,6 +423,18 @@ def tamd_attention_forward(module, query, key, value, attention_mask, dropout: f
     if used is not None and used < sk:
         sk = used  # pre-allocated cache: only the first kv_len key slots are in use (strided views of the cache)
         k, v = k[:, :sk], v[:, :sk]
+    window = attention_mask.window if isinstance(attention_mask, TamdMask) else None
+    if window is not None:
+        # a multi-token step over a sliding-window cache (tamd_mask): K / V are the L keys the cache returned, the bound is
+        # computed in the kernel -- no planes, and the `sliding_window` keyword below says nothing more
+        if not causal or sq < 2 or (used is not None and used != key.shape[2]) or attention_mask.q_start is not None \
+                or attention_mask.kv_len is not None or drop_p:
+            raise TamdError(f"attn_implementation='tamd': a sliding-window cache step needs causal attention of >= 2 queries "
+                            f"over exactly the keys its mask covers, without dropout (got {sq} queries over {key.shape[2]} "
+                            f"keys, mask over {used}, causal={causal}, dropout={drop_p})")
+        key_valid = None if attention_mask.key_valid is None else _key_valid_from_mask(attention_mask.key_valid, b, sk)
+        q, k, v = (t if t.stride(3) == 1 else t.contiguous() for t in (q, k, v))
+        return ops.attention(q, k, v, float(scaling), True, key_valid, window=int(window)), None
     key_valid, q_start, kv_len = split_mask_kv(attention_mask, b, sk)
     q_start = varlen_q_start(q_start, kwargs, b, sq, sk, causal)
     q_start = window_q_start(q_start, kwargs.get("sliding_window"), b, sq, sk, causal, q.device)

@@ -67,6 +67,18 @@ int attn_fwd_launch(const AttnArgs& a, bool causal, hipStream_t s) {
   return launch_status();
 }
 
+// the causal forward under a sliding window (tamd_attn_fwd_window): the WINDOW instantiations, no dropout
+template <typename T, int D>
+int attn_fwd_window_launch(const AttnArgs& a, hipStream_t s) {
+  const size_t smem = (size_t)4 * kKB * D * 2;
+  dim3 grid((unsigned)(a.nqt * a.heads_q * a.batch)), block(kAttnThreads);
+  if (a.key_valid != nullptr)
+    hipLaunchKernelGGL((attn_fwd_kernel<T, D, true, true, false, false, false, true>), grid, block, smem, s, a);
+  else
+    hipLaunchKernelGGL((attn_fwd_kernel<T, D, true, false, false, false, false, true>), grid, block, smem, s, a);
+  return launch_status();
+}
+
 // split-KV forward + merge (tamd_attn_decode).  No dropout, no packed sequences (checked by the caller).  The grid and the
 // workspace follow the plan, which follows seq_k -- the allocation -- also when the key counts come from a.seq_k_dev: a piece
 // whose tiles lie behind its row's count loads nothing and leaves with weight 0.
@@ -75,7 +87,12 @@ int attn_decode_launch(const AttnArgs& a, bool causal, hipStream_t s) {
   const size_t smem = (size_t)4 * kKB * D * 2;
   dim3 grid((unsigned)(a.nqt * a.heads_q * a.batch * a.kv_splits)), block(kAttnThreads);
 #define TAMD_AD(C_, L_) hipLaunchKernelGGL((attn_fwd_kernel<T, D, C_, true, false, true, L_>), grid, block, smem, s, a)
-  if (a.seq_k_dev != nullptr) {  // key counts in device memory: the DEVLEN instantiations
+  if (a.window > 0) {  // a sliding window (tamd_attn_decode_window): the WINDOW instantiations, key counts from the host
+    if (causal)
+      hipLaunchKernelGGL((attn_fwd_kernel<T, D, true, true, false, true, false, true>), grid, block, smem, s, a);
+    else
+      hipLaunchKernelGGL((attn_fwd_kernel<T, D, false, true, false, true, false, true>), grid, block, smem, s, a);
+  } else if (a.seq_k_dev != nullptr) {  // key counts in device memory: the DEVLEN instantiations
     if (causal)
       TAMD_AD(true, true);
     else
@@ -160,6 +177,7 @@ AttnArgs make_args(const tamd_attn_params* p) {
   a.kv_splits = 1;
   a.tiles_per_split = 0;
   a.seq_k_dev = nullptr;  // (tamd_attn_decode alone honours tamd_attn_params.seq_k_dev, and sets it there)
+  a.window = 0;           // (the two window entry points set it)
 #ifdef TAMD_DIAG
   a.trace = g_attn_trace;
 #else
@@ -245,11 +263,9 @@ extern "C" size_t tamd_attn_decode_workspace_bytes(const struct tamd_attn_params
   const size_t rows = (size_t)d.splits * (size_t)d.p.batch * (size_t)d.p.seq_q * (size_t)d.p.heads_q;
   return rows * ((size_t)d.p.head_dim + 1) * sizeof(float);
 }
-extern "C" int tamd_attn_decode(const struct tamd_attn_params* p0, void* workspace, size_t workspace_bytes,
-                                tamd_stream_t stream) {
-  const int chk = attn_check(p0);
-  if (chk != TAMD_OK) return chk;
-  if (p0->dropout_p != 0.f || p0->q_start != nullptr) return TAMD_E_ARG;  // (with or without seq_k_dev)
+// window > 0: tamd_attn_decode_window (checked there)
+static int attn_decode_run(const tamd_attn_params* p0, int64_t window, void* workspace, size_t workspace_bytes,
+                           tamd_stream_t stream) {
   if (!workspace) return TAMD_E_NULL;
   if (workspace_bytes < tamd_attn_decode_workspace_bytes(p0) || !aligned16(workspace)) return TAMD_E_WORKSPACE;
   const DecodePlan d = decode_plan(p0);
@@ -258,6 +274,9 @@ extern "C" int tamd_attn_decode(const struct tamd_attn_params* p0, void* workspa
   a.kv_splits = d.splits;
   a.tiles_per_split = d.tiles_per_split;
   a.seq_k_dev = reinterpret_cast<const int*>(d.p.seq_k_dev);  // (decode_plan re-strides rows and heads, never the batch)
+  // (one query row whose heads became the rows of the tile: the plan made the call non-causal, and in the non-causal WINDOW
+  // instantiations every row is the query at the last position -- the bound is seq_k - window for all of them)
+  a.window = (int)(window < p0->seq_k ? window : p0->seq_k);
   const size_t rows = (size_t)d.splits * (size_t)d.p.batch * (size_t)d.p.seq_q * (size_t)d.p.heads_q;
   a.o_part = reinterpret_cast<float*>(workspace);
   a.lse_part = a.o_part + rows * (size_t)d.p.head_dim;
@@ -268,6 +287,44 @@ extern "C" int tamd_attn_decode(const struct tamd_attn_params* p0, void* workspa
     TAMD_DISPATCH_HALF(d.p.dtype, return (attn_decode_launch<T, 64>(a, d.p.causal != 0, s)));
   }
   return TAMD_E_DTYPE;
+}
+extern "C" int tamd_attn_decode(const struct tamd_attn_params* p0, void* workspace, size_t workspace_bytes,
+                                tamd_stream_t stream) {
+  const int chk = attn_check(p0);
+  if (chk != TAMD_OK) return chk;
+  if (p0->dropout_p != 0.f || p0->q_start != nullptr) return TAMD_E_ARG;  // (with or without seq_k_dev)
+  return attn_decode_run(p0, 0, workspace, workspace_bytes, stream);
+}
+
+// ---- a causal sliding window over a KV cache (inference; the reference: sliding_window_overlay, masking_utils.py:92-101, over
+// the keys a DynamicSlidingWindowLayer / StaticSlidingWindowLayer returns, cache_utils.py:203-277, :504-628): a multi-token
+// step -- a prompt chunk, a second chat turn, a block of speculative tokens -- whose first rows no longer see the oldest keys
+static int attn_window_check(const tamd_attn_params* p, int64_t window) {
+  const int chk = attn_check(p);
+  if (chk != TAMD_OK) return chk;
+  if (window < 1 || p->seq_q > p->seq_k || (p->seq_q > 1 && !p->causal)) return TAMD_E_ARG;
+  if (p->q_start != nullptr || p->dropout_p != 0.f || p->seq_k_dev != nullptr) return TAMD_E_ARG;
+  return TAMD_OK;
+}
+extern "C" int tamd_attn_fwd_window(const struct tamd_attn_params* p, int64_t window, tamd_stream_t stream) {
+  const int chk = attn_window_check(p, window);
+  if (chk != TAMD_OK) return chk;
+  AttnArgs a = make_args(p);
+  a.window = (int)(window < p->seq_k ? window : p->seq_k);
+  hipStream_t s = TAMD_STREAM(stream);
+  // (one query row sees every key down to seq_k - window with or without `causal`: the causal instantiation computes that)
+  if (p->head_dim == 128) {
+    TAMD_DISPATCH_HALF(p->dtype, return (attn_fwd_window_launch<T, 128>(a, s)));
+  } else {
+    TAMD_DISPATCH_HALF(p->dtype, return (attn_fwd_window_launch<T, 64>(a, s)));
+  }
+  return TAMD_E_DTYPE;
+}
+extern "C" int tamd_attn_decode_window(const struct tamd_attn_params* p, int64_t window, void* workspace,
+                                       size_t workspace_bytes, tamd_stream_t stream) {
+  const int chk = attn_window_check(p, window);
+  if (chk != TAMD_OK) return chk;
+  return attn_decode_run(p, window, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tamd_attn_bwd(const struct tamd_attn_bwd_params* p, tamd_stream_t stream) {

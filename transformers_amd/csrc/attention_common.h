@@ -51,6 +51,9 @@ struct AttnArgs {
   // tamd_attn_params.seq_k_dev), or null.  Row b is the problem with clamp(seq_k_dev[b], 0, seq_k) keys; seq_k stays the
   // allocation (plan, key_valid stride)
   const int* seq_k_dev;
+  // the WINDOW instantiations only (tamd_attn_fwd_window / tamd_attn_decode_window): the causal sliding window, 1 .. seq_k keys.
+  // Last, so that every field above keeps its place in the argument block
+  int window;
 };
 
 // Diagnostic build only: phase i of the forward tile loop ends here (s_memtime stamps of workgroup 0, summed per wave)
@@ -363,6 +366,22 @@ __device__ __forceinline__ int wave_uniform_i32(int v) {
 // first visible key of query row `qrow` (0 when sequences are not packed) and its wave-wide max / min
 __device__ __forceinline__ int packed_klo(const AttnArgs& a, int b, int qrow) {
   return (a.q_start != nullptr && qrow < a.seq_q) ? a.q_start[(int64_t)b * a.seq_q + qrow] : 0;
+}
+
+// a per-lane value the compiler may not look through (an empty asm: no instruction): it stays the one register it is
+__device__ __forceinline__ int opaque_vgpr_i32(int v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(v));
+#endif
+  return v;
+}
+
+// first visible key of a query that stands at position `pos` among the keys, under the sliding window a.window:
+// max(0, pos - W + 1).  pos = row + seq_k - seq_q under the causal mask; seq_k - 1 for every row of a call without it (one query
+// row -- possibly re-strided so that its heads are the rows of the tile -- stands at the last key)
+__device__ __forceinline__ int window_klo(const AttnArgs& a, int pos) {
+  const int lo = pos - a.window + 1;
+  return lo > 0 ? lo : 0;
 }
 
 constexpr int kKVB = 128;  // keys per workgroup in the dK/dV kernel (32 per wave)

@@ -13,7 +13,14 @@
 // leave as "saw no key".  (A template argument, not a test of the pointer inside the SPLIT kernels: with the test there the
 // calls WITHOUT counts ran 0.4 us slower at every shape and 1.4 us at 8 query rows x 4096 keys, 23.5 against 22.1 -- the same
 // loop, another order of the prologue's scalar loads; as it is they run the code they ran before.)
-template <typename T, int D, bool CAUSAL, bool HAS_MASK, bool DROP, bool SPLIT = false, bool DEVLEN = false>
+// WINDOW (tamd_attn_fwd_window / tamd_attn_decode_window; a.window): a causal sliding window over a KV cache -- query row s sees
+// the keys max(0, s + off - W + 1) .. s + off.  The lower bound takes the place of the packed-sequence plane: computed from the
+// row index, no plane read; it does not decrease along the rows, so the wave-uniform bounds are those of the wave's first and
+// last live row, and the block's first tile that of its first row.  Everything behind that is the machinery the planes use.
+// Without CAUSAL (SPLIT only: one query row, its heads re-strided into the rows of the tile) every row stands at the last key.
+// (A template argument for the reason DEVLEN is one: the instantiations without it are the code they were,
+// profiles/attn_window_isa.md.)
+template <typename T, int D, bool CAUSAL, bool HAS_MASK, bool DROP, bool SPLIT = false, bool DEVLEN = false, bool WINDOW = false>
 // (two workgroups per CU where the registers allow it: the dropout variants at D = 128 need more than 256)
 // (three at head_dim 64 without padding mask / dropout -- CLIP: the kernel sat at 155 registers before the resident -m tuple)
 __global__ __launch_bounds__(kAttnThreads, (DROP && D > 64) ? 1 : ((D == 64 && !HAS_MASK && !DROP) ? 3 : 2)) void attn_fwd_kernel(AttnArgs a) {
@@ -77,8 +84,24 @@ __global__ __launch_bounds__(kAttnThreads, (DROP && D > 64) ? 1 : ((D == 64 && !
   for (int ks = 0; ks < KS; ++ks) qf[ks] = scale_frag<T>(qf[ks], a.scale_log2, !a.q_prescaled);
 
   // packed sequences: this query's first visible key; wave-uniform bounds for tile skipping / mask-free tiles
-  const int klo = packed_klo(a, b, qrow);
-  const int klo_max = (int)wave_max((float)klo), klo_min = -(int)wave_max(-(float)klo);
+  static_assert(!WINDOW || (!DROP && !DEVLEN), "the window instantiations: inference, key counts from the host");
+  int klo, klo_max, klo_min;
+  if constexpr (WINDOW) {
+    // ... a sliding window: the bound follows from the row's position among the keys -- row + off under the causal mask, the
+    // last key's for every row without it (one query row whose heads became the rows of the tile: attention.hip decode_plan).
+    // Scalars for a wave's first and last live row
+    const int last = qw0 + 31 < a.seq_q ? qw0 + 31 : a.seq_q - 1;
+    klo_min = window_klo(a, CAUSAL ? qw0 + off : seq_k - 1);
+    klo_max = window_klo(a, CAUSAL ? last + off : seq_k - 1);
+    klo = CAUSAL ? window_klo(a, qrow + off) : klo_min;  // (without the causal mask: one bound for all rows)
+    // the lane's bound is ONE register from here on, as the plane's value is in the other instantiations (left transparent, the
+    // mask arithmetic of the 32 elements was rewritten around row + off - W and hoisted out of the tile loop: scratch,
+    // profiles/attn_window_isa.md)
+    if constexpr (CAUSAL) klo = opaque_vgpr_i32(klo);
+  } else {
+    klo = packed_klo(a, b, qrow);
+    klo_max = (int)wave_max((float)klo), klo_min = -(int)wave_max(-(float)klo);
+  }
 
   f32x16 oacc[DT];
 #pragma unroll
@@ -133,7 +156,8 @@ __global__ __launch_bounds__(kAttnThreads, (DROP && D > 64) ? 1 : ((D == 64 && !
   };
   // packed sequences: q_start is non-decreasing along a row, so no row of this block sees a key before the first
   // visible key of its first row: whole K/V tiles below it are neither loaded nor visited (buffers alternate from t0)
-  const int t0f = (q0 < a.seq_q ? packed_klo(a, b, q0) : 0) / kKB;
+  // (a sliding window: the same, with the bound of the block's first row)
+  const int t0f = (WINDOW ? window_klo(a, CAUSAL ? q0 + off : seq_k - 1) : (q0 < a.seq_q ? packed_klo(a, b, q0) : 0)) / kKB;
   // the key tiles this workgroup visits: [t0, nkt_w) -- all of them, or this split's share
   const int t0 = SPLIT ? (t0f > split * a.tiles_per_split ? t0f : split * a.tiles_per_split) : t0f;
   const int nkt_w = SPLIT ? (nkt < (split + 1) * a.tiles_per_split ? nkt : (split + 1) * a.tiles_per_split) : nkt;

@@ -44,7 +44,7 @@ using OptTensor = std::optional<at::Tensor>;
   X(tamd_add) X(tamd_adamw_step) X(tamd_mt_sumsq) X(tamd_mt_norm_finish) X(tamd_mt_scale) X(tamd_mt_adamw_step) X(tamd_sr_bits) X(tamd_sr_round) X(tamd_mt_adamw_step_sr) X(tamd_colsum_workspace_bytes) X(tamd_colsum) X(tamd_transpose)                      \
   X(tamd_cross_entropy_fwd) X(tamd_cross_entropy_bwd) X(tamd_gemm) X(tamd_gemm_workspace_bytes) X(tamd_gemm_ws)       \
   X(tamd_gemm_swiglu) X(tamd_gemm_swiglu_bwd) X(tamd_gemm_colscale) X(tamd_gemm_seg) X(tamd_gemm_group_workspace_bytes) X(tamd_gemm_group) X(tamd_attn_fwd) X(tamd_attn_bwd)   \
-  X(tamd_attn_decode_workspace_bytes) X(tamd_attn_decode)                                                            \
+  X(tamd_attn_decode_workspace_bytes) X(tamd_attn_decode) X(tamd_attn_fwd_window) X(tamd_attn_decode_window)          \
   X(tamd_moe_route_workspace_bytes) X(tamd_moe_route) X(tamd_moe_gather) X(tamd_moe_combine) X(tamd_moe_combine_bwd) \
   X(tamd_gemm_routed)
 
@@ -1236,6 +1236,26 @@ std::tuple<Tensor, Tensor> k_attn_fwd(const Tensor& q, const Tensor& k, const Te
   return {o, lse};
 }
 
+// the same under a causal sliding window over a KV cache (include/tamd.h tamd_attn_fwd_window / tamd_attn_decode_window):
+// inference only; the schedule is picked by the rule above
+std::tuple<Tensor, Tensor> k_attn_window(const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal,
+                                         const OptTensor& key_valid_, int64_t window, bool need_lse) {
+  Launch L({&q, &k, &v, p(key_valid_)});
+  Tensor o = at::empty({q.size(0), q.size(1), q.size(2), q.size(3)}, q.options());
+  Tensor lse = need_lse ? f32_like(q, {q.size(0), q.size(2), q.size(1)}) : Tensor();
+  Tensor key_valid = checked_key_valid(key_valid_, q, k);
+  tamd_attn_params ap{};
+  fill_attn_params(&ap, q, k, v, o, lse, key_valid, scale, causal, 0.0, 0, Tensor());
+  if (kDecodeKernel && q.size(1) <= kDecodeMaxRows && k.size(1) >= kDecodeMinKeys) {
+    const size_t nbytes = api().tamd_attn_decode_workspace_bytes(&ap);
+    Tensor ws = at::empty({(int64_t)nbytes}, q.options().dtype(at::kByte));
+    check(api().tamd_attn_decode_window(&ap, window, mptr(ws), nbytes, L.stream), "tamd_attn_decode_window");
+    return {o, lse};
+  }
+  check(api().tamd_attn_fwd_window(&ap, window, L.stream), "tamd_attn_fwd_window");
+  return {o, lse};
+}
+
 // gradients written into dq / dk / dv (views with the strides of q / k / v) or freshly allocated.  rope = (cos, sin): q and k
 // had been rotated before the attention, dq and dk leave through the transposed rotation.
 std::tuple<Tensor, Tensor, Tensor> k_attn_bwd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
@@ -1381,6 +1401,12 @@ std::tuple<Tensor, Tensor> op_attn_fwd(const Tensor& q_, const Tensor& k_, const
   const Tensor q = attn_operand(q_), k = attn_operand(k_), v = attn_operand(v_);
   auto [o, lse] = k_attn_fwd(q, k, v, scale, causal, key_valid, need_lse, dropout_p, seed, q_start, false, seed_word(seed_dev, 0),
                              kv_len);
+  return {o, lse.defined() ? lse : nothing(q)};
+}
+std::tuple<Tensor, Tensor> op_attn_window(const Tensor& q_, const Tensor& k_, const Tensor& v_, double scale, bool causal,
+                                          const OptTensor& key_valid, int64_t window, bool need_lse) {
+  const Tensor q = attn_operand(q_), k = attn_operand(k_), v = attn_operand(v_);
+  auto [o, lse] = k_attn_window(q, k, v, scale, causal, key_valid, window, need_lse);
   return {o, lse.defined() ? lse : nothing(q)};
 }
 std::tuple<Tensor, Tensor, Tensor> op_attn_bwd(const Tensor& q_, const Tensor& k_, const Tensor& v_, const Tensor& o_,
@@ -1881,6 +1907,8 @@ TORCH_LIBRARY(tamd, m) {
   m.def("gemm_colscale(Tensor x2, Tensor w, Tensor? bias, int scale_cols, float col_scale) -> Tensor");
   m.def("attn_fwd(Tensor q, Tensor k, Tensor v, float scale, bool causal, Tensor? key_valid=None, bool need_lse=True, "
         "float dropout_p=0.0, int seed=0, Tensor? q_start=None, Tensor? seed_dev=None, Tensor? kv_len=None) -> (Tensor, Tensor)");
+  m.def("attn_window(Tensor q, Tensor k, Tensor v, float scale, bool causal, Tensor? key_valid, int window, "
+        "bool need_lse=True) -> (Tensor, Tensor)");
   m.def("attn_bwd(Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor dout, float scale, bool causal, "
         "Tensor? key_valid=None, float dropout_p=0.0, int seed=0, Tensor? q_start=None, Tensor? rope_cos=None, "
         "Tensor? rope_sin=None, Tensor? seed_dev=None) -> (Tensor, Tensor, Tensor)");
@@ -1987,6 +2015,7 @@ TORCH_LIBRARY(tamd, m) {
   m.impl("gemm_swiglu", &op_gemm_swiglu);                            \
   m.impl("gemm_swiglu_bwd", &k_gemm_swiglu_bwd);                     \
   m.impl("attn_fwd", &op_attn_fwd);                                  \
+  m.impl("attn_window", &op_attn_window);                            \
   m.impl("attn_bwd", &op_attn_bwd);                                  \
   m.impl("attn_bwd_out", &op_attn_bwd_out);                          \
   m.impl("rmsnorm", &op_rmsnorm);                                    \

@@ -295,11 +295,26 @@ def raw_gemm_swiglu_bwd(dy, wd, gu):
     return T.gemm_swiglu_bwd(dy, wd, gu)
 
 
+def _check_window(window, dropout_p, q_start, kv_len) -> int:
+    if isinstance(window, bool) or int(window) != window or int(window) < 1:
+        raise TamdError(f"a sliding window is a positive number of keys, got {window!r}")
+    if dropout_p or q_start is not None or kv_len is not None:
+        raise TamdError("attention under a sliding window over a KV cache (window) is an inference path: it takes no dropout, "
+                        "no packed-sequence bounds and no key counts in device memory")
+    return int(window)
+
+
 def raw_attn_fwd(q, k, v, scale, causal, key_valid=None, need_lse=True, dropout_p=0.0, seed=0, q_start=None, seed_dev=None,
-                 kv_len=None):
+                 kv_len=None, window=None):
     """q [B,Sq,Hq,D], k/v [B,Sk,Hkv,D] (strided views fine) -> o [B,Sq,Hq,D] contiguous, lse [B,Hq,Sq] fp32.
     kv_len (int32 [B] on the device, or None): the key slots in use per batch row -- k / v are a pre-allocated cache, row b is
-    computed as if they had been sliced to kv_len[b] rows (include/tamd.h seq_k_dev; always the split-KV decode kernel)."""
+    computed as if they had been sliced to kv_len[b] rows (include/tamd.h seq_k_dev; always the split-KV decode kernel).
+    window (int or None): a causal sliding window over a KV cache -- query s sees the keys s + off - window + 1 .. s + off,
+    off = Sk - Sq (include/tamd.h tamd_attn_fwd_window / tamd_attn_decode_window, picked by the shape like the plain call)."""
+    if window is not None:
+        o, lse = T.attn_window(q, k, v, float(scale), bool(causal), key_valid, _check_window(window, dropout_p, q_start, kv_len),
+                               need_lse)
+        return o, (lse if need_lse else None)
     o, lse = T.attn_fwd(q, k, v, float(scale), bool(causal), key_valid, need_lse, float(dropout_p),
                         int(seed) & 0x7FFFFFFFFFFFFFFF, q_start, seed_dev, kv_len)
     return o, (lse if need_lse else None)
@@ -485,6 +500,8 @@ register("gemm_swiglu", lambda x2, wgu, need_gu=True: (x2.new_empty(x2.shape[0],
 register("gemm_swiglu_bwd", lambda dy, wd, gu: torch.empty_like(gu))
 register("attn_fwd", lambda q, k, v, scale, causal, key_valid=None, need_lse=True, dropout_p=0.0, seed=0, q_start=None, seed_dev=None,
          kv_len=None: (
+    q.new_empty(q.shape), _f32(q, q.shape[0], q.shape[2], q.shape[1]) if need_lse else _nothing(q)))
+register("attn_window", lambda q, k, v, scale, causal, key_valid, window, need_lse=True: (
     q.new_empty(q.shape), _f32(q, q.shape[0], q.shape[2], q.shape[1]) if need_lse else _nothing(q)))
 register("attn_bwd", lambda q, k, v, o, lse, dout, scale, causal, key_valid=None, dropout_p=0.0, seed=0, q_start=None,
          rope_cos=None, rope_sin=None, seed_dev=None: (
@@ -1100,12 +1117,19 @@ def dropout_keep_mask(seed: int, batch: int, heads: int, seq_q: int, seq_k: int,
     return torch.from_numpy((field >= thr16).reshape(batch, heads, seq_q, seq_k))
 
 
-def attention(q, k, v, scale, causal, key_valid=None, dropout_p=0.0, seed=None, q_start=None, seed_dev=None, kv_len=None):
+def attention(q, k, v, scale, causal, key_valid=None, dropout_p=0.0, seed=None, q_start=None, seed_dev=None, kv_len=None,
+              window=None):
     """kv_len (int32 [B] on the device, or None): k / v are a pre-allocated cache of which row b uses the first kv_len[b] slots
-    (see raw_attn_fwd) -- inference only: a call that would be differentiated is refused."""
+    (see raw_attn_fwd) -- inference only: a call that would be differentiated is refused.
+    window (int or None): a causal sliding window over a KV cache (see raw_attn_fwd) -- inference only, refused likewise."""
     if dropout_p > 0.0 and seed is None and seed_dev is None:
         (seed,), seed_dev = dropout_seeds(1, q.device)
     train = _wants_grad(q, k, v)
+    if window is not None:
+        window = _check_window(window, dropout_p, q_start, kv_len)
+        if train:
+            raise TamdError("attention under a sliding window over a KV cache (window) is an inference path: it has no backward")
+        return T.attn_window(q, k, v, float(scale), bool(causal), key_valid, window, False)[0]
     if kv_len is not None and train:
         raise TamdError("attention over key counts in device memory (kv_len) is an inference path: it has no backward")
     return T.attention(q, k, v, key_valid, float(scale), bool(causal), float(dropout_p), int(seed or 0), q_start,
