@@ -371,6 +371,32 @@ int tamd_gemm_routed(const void* A, const void* B, void* C, void* C2, const int3
                      int64_t rows_pad, int64_t experts, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
                      int64_t ldc, int64_t ldc2, int64_t b_stride, int flags, int epilogue, int dtype, tamd_stream_t stream);
 
+/* The same experts for a cached decode step: few tokens, nothing differentiated (MixtralExperts.forward /
+ * integrations/moe.py grouped_mm_experts_forward with hidden_states [batch, hidden]).  Weight-streaming kernels on the lines of
+ * csrc/gemv.hip (csrc/gemv_moe.inc) that read exactly the weights of the experts that were chosen: no plan, no sorted
+ * buffers, no padding.  Buffers are PAIR-MAJOR: row p = t * top_k + j belongs to pair (t, j).  Three launches per pair of
+ * calls, deterministic, no atomics, no host synchronisation.  An id outside [0, E) (moe.py's expert-parallel sentinel) never
+ * indexes memory, its act / ys rows are NOT written, and it contributes zero to out.
+ * Contract: bf16 / f16; hidden % 64 == 0; inter % 8 == 0; ldact >= inter, ldact % 8 == 0; experts <= 256;
+ * 1 <= tokens <= TAMD_MOE_GEMV_MAX_TOKENS; tokens * top_k <= TAMD_MOE_GEMV_MAX_PAIRS; 16-byte aligned matrices.
+ * Results agree with the routed path to fp32 summation order over K (same roundings). */
+#define TAMD_MOE_GEMV_MAX_TOKENS 16
+#define TAMD_MOE_GEMV_MAX_PAIRS 256
+/* act[p, i] = rT( rT(silu(rT(g))) * rT(u) ), g = x[t] . gate_up[e, i, :], u = x[t] . gate_up[e, inter + i, :], e = top_k_index[p]
+ * (moe.py: `_grouped_mm(hidden_states[token_idx], gate_up_proj)` + `act_fn(gate) * up`; MixtralExperts: nn.functional.linear
+ * (current_state, gate_up_proj[e]).chunk(2)): x [tokens, hidden], gate_up [E, 2 inter, hidden], act [S, inter] (ldact);
+ * the roundings of tamd_gemm_swiglu.  One launch. */
+int tamd_moe_gemv_swiglu(const void* x, const int64_t* top_k_index, const void* gate_up, void* act, int64_t tokens,
+                         int64_t top_k, int64_t experts, int64_t hidden, int64_t inter, int64_t ldact, int dtype,
+                         tamd_stream_t stream);
+/* ys[p, h] = rT( act[p, :] . down[e, h, :] )  (moe.py: `_grouped_mm(.., down_proj)`; MixtralExperts: nn.functional.linear(..,
+ * down_proj[e])), then out[t] = rT( sum_j r32( w[t, j] * f32(ys[t top_k + j]) ) ), j ascending, sentinel pairs skipped -- the
+ * chain of tamd_moe_combine (moe.py: `* top_k_weights` and index_add_).  down [E, hidden, inter], w [tokens, top_k] in
+ * w_dtype = TAMD_F32 or `dtype`, ys [S, hidden] workspace, out [tokens, hidden].  Two launches. */
+int tamd_moe_gemv_down(const void* act, const int64_t* top_k_index, const void* down, const void* w, void* ys, void* out,
+                       int64_t tokens, int64_t top_k, int64_t experts, int64_t hidden, int64_t inter, int64_t ldact,
+                       int w_dtype, int dtype, tamd_stream_t stream);
+
 /* ------------------------------------------------------------------ attention (MFMA, flash-style) */
 
 /* Scaled-dot-product attention replacing eager_attention_forward / repeat_kv

@@ -100,7 +100,9 @@ SIGNATURES = {
     "tamd_moe_combine": (c_int, [P, P, P, P, I64, I64, I64, c_int, c_int, P]),
     "tamd_moe_combine_bwd": (c_int, [P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, c_int, c_int, P]),
     "tamd_gemm_routed": (c_int, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, c_int, c_int, c_int, P]),
-    "tamd_dropout_hash": (ctypes.c_uint32, [ctypes.c_uint64, ctypes.c_uint64]),
+    "tamd_moe_gemv_swiglu": (c_int, [P, P, P, P, I64, I64, I64, I64, I64, I64, c_int, P]),
+    "tamd_moe_gemv_down": (c_int, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, c_int, c_int, P]),
+    "tamd_dropout_hash":(ctypes.c_uint32, [ctypes.c_uint64, ctypes.c_uint64]),
     "tamd_attn_dropout_field": (ctypes.c_uint32, [ctypes.c_uint64] * 6),
     "tamd_attn_fwd": (c_int, [POINTER(AttnParams), P]),
     "tamd_attn_decode_workspace_bytes": (c_size_t, [POINTER(AttnParams)]),

@@ -331,3 +331,6 @@ int gemv_run(const GemvArgs& g, int epilogue, int dtype, hipStream_t stream) {
 }
 
 }  // namespace tamd
+
+// the experts of a mixture-of-experts block on the same stream (tamd_moe_gemv_swiglu / tamd_moe_gemv_down)
+#include "gemv_moe.inc"

@@ -46,7 +46,7 @@ using OptTensor = std::optional<at::Tensor>;
   X(tamd_gemm_swiglu) X(tamd_gemm_swiglu_bwd) X(tamd_gemm_colscale) X(tamd_gemm_seg) X(tamd_gemm_group_workspace_bytes) X(tamd_gemm_group) X(tamd_attn_fwd) X(tamd_attn_bwd)   \
   X(tamd_attn_decode_workspace_bytes) X(tamd_attn_decode) X(tamd_attn_fwd_window) X(tamd_attn_decode_window)          \
   X(tamd_moe_route_workspace_bytes) X(tamd_moe_route) X(tamd_moe_gather) X(tamd_moe_combine) X(tamd_moe_combine_bwd) \
-  X(tamd_gemm_routed)
+  X(tamd_gemm_routed) X(tamd_moe_gemv_swiglu) X(tamd_moe_gemv_down)
 
 struct Api {
   void* handle = nullptr;
@@ -1041,6 +1041,32 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> op_moe_experts_bwd(const Tensor& dout
   return {dx, dw, dgate_up, ddown};
 }
 
+// The same experts for a cached decode step (forward only; csrc/gemv_moe.inc): the weights of the experts that were chosen
+// are streamed once over pair-major buffers -- act [S, I] and ys [S, H], S = T k; nothing proportional to E is allocated, no
+// plan is made.  Three launches.  ops.moe_experts takes this op for few tokens when nothing will be differentiated.
+Tensor op_moe_experts_decode(const Tensor& x, const Tensor& top_k_index, const Tensor& top_k_weights, const Tensor& gate_up,
+                             const Tensor& down) {
+  TORCH_CHECK(x.dim() == 2 && gate_up.dim() == 3 && down.dim() == 3 && top_k_index.dim() == 2 && top_k_index.size(0) == x.size(0) &&
+                  top_k_index.scalar_type() == at::kLong && top_k_weights.sizes() == top_k_index.sizes(),
+              "tamd: moe_experts_decode takes x [T, H], top_k_index (int64) / top_k_weights [T, k], gate_up [E, 2I, H], down [E, H, I]");
+  const int64_t t = x.size(0), h = x.size(1), k = top_k_index.size(1), e = gate_up.size(0), inter = down.size(2);
+  TORCH_CHECK(gate_up.size(1) == 2 * inter && gate_up.size(2) == h && down.size(0) == e && down.size(1) == h &&
+                  gate_up.scalar_type() == x.scalar_type() && down.scalar_type() == x.scalar_type(),
+              "tamd: moe_experts_decode: gate_up [E, 2I, H] and down [E, H, I] do not match x");
+  TORCH_CHECK(t >= 1 && t <= TAMD_MOE_GEMV_MAX_TOKENS && t * k <= TAMD_MOE_GEMV_MAX_PAIRS, "tamd: moe_experts_decode takes 1 .. ",
+              TAMD_MOE_GEMV_MAX_TOKENS, " tokens and at most ", TAMD_MOE_GEMV_MAX_PAIRS, " (token, expert) pairs");
+  const Tensor xc = contig(x), idx = contig(top_k_index), w = contig(top_k_weights), wgu = contig(gate_up), wd = contig(down);
+  Tensor act = at::empty({t * k, inter}, x.options()), ys = at::empty({t * k, h}, x.options()), out = at::empty({t, h}, x.options());
+  Launch L({&xc, &idx, &w, &wgu, &wd});
+  check(api().tamd_moe_gemv_swiglu(ptr(xc), (const int64_t*)ptr(idx), ptr(wgu), mptr(act), t, k, e, h, inter, inter, code_of(x),
+                                   L.stream),
+        "tamd_moe_gemv_swiglu");
+  check(api().tamd_moe_gemv_down(ptr(act), (const int64_t*)ptr(idx), ptr(wd), ptr(w), mptr(ys), mptr(out), t, k, e, h, inter, inter,
+                                 code_of(w), code_of(x), L.stream),
+        "tamd_moe_gemv_down");
+  return out;
+}
+
 // kernel-level ops (tests, tools): outputs are the caller's buffers
 void op_moe_route_out(Tensor& count, Tensor& offset, Tensor& pos, Tensor& tiles, const Tensor& idx, int64_t experts) {
   k_moe_route(idx, experts, count, offset, pos, tiles);
@@ -1935,6 +1961,7 @@ TORCH_LIBRARY(tamd, m) {
   m.def("gemm_routed_out(Tensor(a!) c, Tensor(b!)? c2, Tensor a, Tensor b, Tensor offset, Tensor tiles, int mode, bool need_c=True) -> ()");
   m.def("moe_experts(Tensor x, Tensor top_k_index, Tensor top_k_weights, Tensor gate_up, Tensor down, bool train) -> "
         "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("moe_experts_decode(Tensor x, Tensor top_k_index, Tensor top_k_weights, Tensor gate_up, Tensor down) -> Tensor");
   m.def("moe_experts_bwd(Tensor dout, Tensor top_k_weights, Tensor gate_up, Tensor down, Tensor pos, Tensor count, Tensor offset, "
         "Tensor tiles, Tensor xs, Tensor gus, Tensor acts, Tensor ys) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("swiglu(Tensor gu) -> Tensor");
@@ -2012,6 +2039,7 @@ TORCH_LIBRARY(tamd, m) {
   m.impl("gemm_routed_out", &op_gemm_routed_out);                    \
   m.impl("moe_experts", &op_moe_experts);                            \
   m.impl("moe_experts_bwd", &op_moe_experts_bwd);                    \
+  m.impl("moe_experts_decode", &op_moe_experts_decode);              \
   m.impl("gemm_swiglu", &op_gemm_swiglu);                            \
   m.impl("gemm_swiglu_bwd", &k_gemm_swiglu_bwd);                     \
   m.impl("attn_fwd", &op_attn_fwd);                                  \

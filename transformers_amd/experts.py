@@ -12,7 +12,11 @@ the one of `grouped_mm_experts_forward`:
 with `self.gate_up_proj` [E, 2I, H] (gate rows, then up rows) and `self.down_proj` [E, H, I] (MixtralExperts,
 models/mixtral/modeling_mixtral.py).  What the kernels take runs as ONE dispatcher op, `torch.ops.tamd.moe_experts`
 (routing plan, gather, gate|up product with the SiLU*up way out, down product, weighted combine; the backward through the same
-plan) -- no host synchronisation, deterministic, no atomics.  Everything else calls the module's ORIGINAL forward and is counted
+plan) -- no host synchronisation, deterministic, no atomics.  A decode-sized call (up to `ops.MOE_GEMV_MAX_TOKENS` tokens,
+nothing to differentiate: the steps of `generate()` after the prefill) runs instead on `torch.ops.tamd.moe_experts_decode`, the
+weight-streaming kernels of csrc/gemv_moe.inc, which read the weights of the chosen experts once and build no plan
+(`decode_call_count()` counts those calls; TAMD_MOE_GEMV=0 in the environment keeps every call on the routed GEMM).
+Everything else calls the module's ORIGINAL forward and is counted
 (`transformers_amd.fallback_calls()`): it is never approximated.
 """
 from __future__ import annotations
@@ -36,6 +40,12 @@ def call_count(reset: bool = False) -> int:
     if reset:
         _calls = 0
     return n
+
+
+def decode_call_count(reset: bool = False) -> int:
+    """Of those calls (and of direct `ops.moe_experts` calls), the ones that took the decode op
+    `torch.ops.tamd.moe_experts_decode` since the last reset."""
+    return ops.moe_decode_call_count(reset)
 
 
 def _refusal(self, hidden_states, top_k_index, top_k_weights):

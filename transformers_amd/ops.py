@@ -23,6 +23,7 @@ missing, or a tensor is not on a GPU, the call raises.
 """
 from __future__ import annotations
 
+import os
 import threading
 from typing import Optional
 
@@ -787,6 +788,8 @@ def _moe_experts_backward(ctx, dout, *_aux):
 
 register("moe_experts_bwd", _moe_experts_bwd_fake)
 register("moe_experts", _moe_experts_fake, _moe_experts_backward, _moe_experts_setup)
+# the decode-step experts (csrc/gemv_moe.inc): forward only, no autograd formula
+register("moe_experts_decode", lambda x, top_k_index, top_k_weights, gate_up, down: x.new_empty(x.shape[0], x.shape[1]))
 
 
 def _bias_act_setup(ctx, inputs, output):
@@ -1037,10 +1040,38 @@ def linear_swiglu(x2, wgu):
     return T.gemm_swiglu(x2, wgu, False)[1]
 
 
+# Decode-sized calls of the experts: up to this many tokens run on the weight-streaming kernels (torch.ops.tamd.moe_experts_decode,
+# csrc/gemv_moe.inc) when nothing will be differentiated; more tokens, and every call that needs a backward, take the routed
+# GEMM.  Where the cut sits is measured: tools/moe_decode_bench.py -> profiles/moe_decode_ab.jsonl.
+# TAMD_MOE_GEMV=0 in the environment (read per call): never -- the A/B switch of that tool and of the tests.
+MOE_GEMV_MAX_TOKENS = 16    # (<= TAMD_MOE_GEMV_MAX_TOKENS of include/tamd.h)
+MOE_GEMV_MAX_PAIRS = 256    # (TAMD_MOE_GEMV_MAX_PAIRS)
+_moe_decode_calls = 0
+
+
+def moe_decode_cut() -> int:
+    """Tokens up to which `moe_experts` takes the decode op (0: never)."""
+    return 0 if os.environ.get("TAMD_MOE_GEMV", "1") == "0" else MOE_GEMV_MAX_TOKENS
+
+
+def moe_decode_call_count(reset: bool = False) -> int:
+    """Calls of `moe_experts` that took torch.ops.tamd.moe_experts_decode since the last reset."""
+    global _moe_decode_calls
+    n = _moe_decode_calls
+    if reset:
+        _moe_decode_calls = 0
+    return n
+
+
 def moe_experts(x, top_k_index, top_k_weights, gate_up_proj, down_proj):
     """The experts module of a gated SiLU mixture-of-experts block: x [T, H], top_k_index int64 [T, k], top_k_weights [T, k]
     (fp32 or x's dtype), gate_up_proj [E, 2I, H] = [gate ; up] rows per expert, down_proj [E, H, I]  ->  [T, H]."""
+    global _moe_decode_calls
     train = _wants_grad(x, top_k_weights, gate_up_proj, down_proj)
+    t = x.shape[0]
+    if not train and 1 <= t <= moe_decode_cut() and top_k_index.numel() <= MOE_GEMV_MAX_PAIRS:
+        _moe_decode_calls += 1
+        return T.moe_experts_decode(x, top_k_index, top_k_weights, gate_up_proj, down_proj)
     return T.moe_experts(x, top_k_index, top_k_weights, gate_up_proj, down_proj, train)[0]
 
 
