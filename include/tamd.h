@@ -397,6 +397,38 @@ int tamd_moe_gemv_down(const void* act, const int64_t* top_k_index, const void* 
                        int64_t tokens, int64_t top_k, int64_t experts, int64_t hidden, int64_t inter, int64_t ldact,
                        int w_dtype, int dtype, tamd_stream_t stream);
 
+/* The router in front of those experts: softmax over the experts, the top_k largest, optional renormalisation -- what follows
+ * the gate product in MixtralTopKRouter.forward (models/mixtral/modeling_mixtral.py: `softmax(router_logits, dtype=float)`,
+ * `torch.topk`, `router_top_value /= router_top_value.sum(-1, keepdim=True)`) and in Qwen3MoeTopKRouter.forward
+ * (models/qwen3_moe/modeling_qwen3_moe.py: the same with `if self.norm_topk_prob` and `.to(router_logits.dtype)`;
+ * Qwen2MoeTopKRouter and OlmoeTopKRouter are the same chain).  Additive under ABI 13.  One launch, one wave per token, no LDS,
+ * no atomics.  logits [tokens, experts] in `dtype` (bf16 / f16) with row stride lde >= experts (elements);
+ * 1 <= top_k <= min(experts, 16); experts <= 256; 1 <= tokens < 2^31; TAMD_E_SHAPE otherwise.  Per token t:
+ *     l_e = f32(logits[t, e])
+ *     m   = max_e l_e
+ *     x_e = exp(l_e - m)                        fp32
+ *     Z   = sum_e x_e                           fp32, fixed order
+ *     p_e = x_e / Z
+ *     e_0 .. e_{k-1}: the k largest by (l_e descending, e ascending) -- chosen on the LOGITS, so a tie never depends on exp
+ *     norm != 0:  s = sum_j p_{e_j} (j ascending),  w_j = p_{e_j} / s         norm == 0:  w_j = p_{e_j}
+ *     w[t, j] = w_j (w_dtype = TAMD_F32) or rT(w_j) (w_dtype = dtype);   top_k_index[t, j] = e_j (int64)
+ * The pairs are ordered as torch.topk(sorted=True) orders them (tamd_moe_combine sums j ascending: the order reaches the model's
+ * bits).  The selection equals torch.topk(softmax(logits)) on every row whose k-th and (k+1)-th probabilities differ; on a tie
+ * torch's choice is unspecified and this one is the LOWER id.  For a row holding a NaN, or only -inf, the values are unspecified
+ * (as the reference's are) and the indices are still top_k distinct ids in [0, experts). */
+int tamd_moe_router_fwd(const void* logits, void* w, int64_t* top_k_index, int64_t tokens, int64_t experts, int64_t top_k,
+                        int64_t lde, int norm, int w_dtype, int dtype, tamd_stream_t stream);
+/* Backward of tamd_moe_router_fwd (what autograd derives for the reference's softmax / topk / sum / div): dlogits [tokens,
+ * experts] in `dtype`, row stride lde, from the same logits, the forward's top_k_index and dw [tokens, top_k] in w_dtype.
+ * m, x, Z, p are recomputed exactly as the forward computes them; nothing else is saved.  g_j = f32(dw[t, j]):
+ *     norm != 0:  c = sum_j r32(g_j * w_j) (j ascending, w_j = p_{e_j} / s in fp32);  dl_{e_j} = w_j (g_j - c);  dl_e = +0 for
+ *                 every unselected e  (exact: renormalised weights are a softmax over the selected logits alone)
+ *     norm == 0:  d = sum_j r32(g_j * p_{e_j}) (j ascending);  dl_e = p_e ((e selected ? g_j : 0) - d)
+ *     dlogits[t, e] = rT(dl_e);   columns experts .. lde - 1 are written as zeros
+ * An id outside [0, experts) in top_k_index is skipped and never indexes memory. */
+int tamd_moe_router_bwd(const void* logits, const int64_t* top_k_index, const void* dw, void* dlogits, int64_t tokens,
+                        int64_t experts, int64_t top_k, int64_t lde, int norm, int w_dtype, int dtype, tamd_stream_t stream);
+
 /* ------------------------------------------------------------------ attention (MFMA, flash-style) */
 
 /* Scaled-dot-product attention replacing eager_attention_forward / repeat_kv

@@ -950,3 +950,5 @@ int tamd_cross_entropy_bwd(const void* logits, const int64_t* labels, const floa
 
 // routing of sparse mixture-of-experts blocks (tamd_moe_route / _gather / _combine / _combine_bwd)
 #include "moe_route.inc"
+// the router in front of them: softmax + top-k, forward and backward (tamd_moe_router_fwd / _bwd)
+#include "moe_router.inc"

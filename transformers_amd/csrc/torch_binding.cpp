@@ -46,7 +46,7 @@ using OptTensor = std::optional<at::Tensor>;
   X(tamd_gemm_swiglu) X(tamd_gemm_swiglu_bwd) X(tamd_gemm_colscale) X(tamd_gemm_seg) X(tamd_gemm_group_workspace_bytes) X(tamd_gemm_group) X(tamd_attn_fwd) X(tamd_attn_bwd)   \
   X(tamd_attn_decode_workspace_bytes) X(tamd_attn_decode) X(tamd_attn_fwd_window) X(tamd_attn_decode_window)          \
   X(tamd_moe_route_workspace_bytes) X(tamd_moe_route) X(tamd_moe_gather) X(tamd_moe_combine) X(tamd_moe_combine_bwd) \
-  X(tamd_gemm_routed) X(tamd_moe_gemv_swiglu) X(tamd_moe_gemv_down)
+  X(tamd_gemm_routed) X(tamd_moe_gemv_swiglu) X(tamd_moe_gemv_down) X(tamd_moe_router_fwd) X(tamd_moe_router_bwd)
 
 struct Api {
   void* handle = nullptr;
@@ -1067,6 +1067,42 @@ Tensor op_moe_experts_decode(const Tensor& x, const Tensor& top_k_index, const T
   return out;
 }
 
+// The router in front of the experts (csrc/moe_router.inc; MixtralTopKRouter.forward / Qwen3MoeTopKRouter.forward after their
+// gate product): logits [T, E] with a row stride >= E (the [:, :E] part of a product over a zero-padded gate weight) ->
+// (weights [T, k] in fp32 or the logits' dtype, indices [T, k] int64).  One launch.
+bool router_strided(const Tensor& t) { return t.dim() == 2 && t.stride(1) == 1 && t.stride(0) >= t.size(1); }
+std::tuple<Tensor, Tensor> op_moe_router(const Tensor& logits, int64_t top_k, bool norm, bool weights_fp32) {
+  TORCH_CHECK(logits.dim() == 2 && (logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kHalf),
+              "tamd: moe_router takes bf16 / fp16 logits [tokens, experts]");
+  const Tensor lg = router_strided(logits) ? logits : logits.contiguous();
+  const int64_t t = lg.size(0), e = lg.size(1);
+  TORCH_CHECK(t >= 1 && e <= 256 && top_k >= 1 && top_k <= 16 && top_k <= e,
+              "tamd: moe_router takes tokens >= 1, experts <= 256 and 1 <= top_k <= min(experts, 16)");
+  Tensor w = at::empty({t, top_k}, lg.options().dtype(weights_fp32 ? at::kFloat : lg.scalar_type()));
+  Tensor idx = at::empty({t, top_k}, lg.options().dtype(at::kLong));
+  Launch L({&lg});
+  check(api().tamd_moe_router_fwd(ptr(lg), mptr(w), (int64_t*)mptr(idx), t, e, top_k, lg.stride(0), norm ? 1 : 0, code_of(w),
+                                  code_of(lg), L.stream),
+        "tamd_moe_router_fwd");
+  return {w, idx};
+}
+// -> dlogits [T, E]: the [:, :E] part of a [T, lde] buffer with the logits' row stride (its columns behind E are zeros)
+Tensor op_moe_router_bwd(const Tensor& dweights, const Tensor& logits, const Tensor& indices, bool norm) {
+  TORCH_CHECK(logits.dim() == 2 && indices.dim() == 2 && indices.scalar_type() == at::kLong && indices.size(0) == logits.size(0) &&
+                  dweights.sizes() == indices.sizes() &&
+                  (dweights.scalar_type() == at::kFloat || dweights.scalar_type() == logits.scalar_type()),
+              "tamd: moe_router_bwd takes logits [T, E], indices (int64) / dweights [T, k] in fp32 or the logits' dtype");
+  const Tensor lg = router_strided(logits) ? logits : logits.contiguous();
+  const Tensor idx = contig(indices), dw = contig(dweights);
+  const int64_t t = lg.size(0), e = lg.size(1), lde = lg.stride(0);
+  Tensor full = at::empty({t, lde}, lg.options());
+  Launch L({&lg, &idx, &dw});
+  check(api().tamd_moe_router_bwd(ptr(lg), (const int64_t*)ptr(idx), ptr(dw), mptr(full), t, e, idx.size(1), lde, norm ? 1 : 0,
+                                  code_of(dw), code_of(lg), L.stream),
+        "tamd_moe_router_bwd");
+  return lde == e ? full : full.narrow(1, 0, e);
+}
+
 // kernel-level ops (tests, tools): outputs are the caller's buffers
 void op_moe_route_out(Tensor& count, Tensor& offset, Tensor& pos, Tensor& tiles, const Tensor& idx, int64_t experts) {
   k_moe_route(idx, experts, count, offset, pos, tiles);
@@ -1964,6 +2000,8 @@ TORCH_LIBRARY(tamd, m) {
   m.def("moe_experts_decode(Tensor x, Tensor top_k_index, Tensor top_k_weights, Tensor gate_up, Tensor down) -> Tensor");
   m.def("moe_experts_bwd(Tensor dout, Tensor top_k_weights, Tensor gate_up, Tensor down, Tensor pos, Tensor count, Tensor offset, "
         "Tensor tiles, Tensor xs, Tensor gus, Tensor acts, Tensor ys) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("moe_router(Tensor logits, int top_k, bool norm, bool weights_fp32) -> (Tensor, Tensor)");
+  m.def("moe_router_bwd(Tensor dweights, Tensor logits, Tensor indices, bool norm) -> Tensor");
   m.def("swiglu(Tensor gu) -> Tensor");
   m.def("bias_act(Tensor x, Tensor? bias, int act) -> Tensor");
   m.def("embedding(Tensor ids, Tensor table, int padding_idx=-1) -> Tensor");
@@ -2040,6 +2078,8 @@ TORCH_LIBRARY(tamd, m) {
   m.impl("moe_experts", &op_moe_experts);                            \
   m.impl("moe_experts_bwd", &op_moe_experts_bwd);                    \
   m.impl("moe_experts_decode", &op_moe_experts_decode);              \
+  m.impl("moe_router", &op_moe_router);                              \
+  m.impl("moe_router_bwd", &op_moe_router_bwd);                      \
   m.impl("gemm_swiglu", &op_gemm_swiglu);                            \
   m.impl("gemm_swiglu_bwd", &k_gemm_swiglu_bwd);                     \
   m.impl("attn_fwd", &op_attn_fwd);                                  \

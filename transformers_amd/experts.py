@@ -48,6 +48,24 @@ def decode_call_count(reset: bool = False) -> int:
     return ops.moe_decode_call_count(reset)
 
 
+_router_calls = 0
+
+
+def router_call_count(reset: bool = False) -> int:
+    """Calls of the replacement routers (models/moe.py) that ran on the kernels (gate product + `ops.moe_router`) since the
+    last reset."""
+    global _router_calls
+    n = _router_calls
+    if reset:
+        _router_calls = 0
+    return n
+
+
+def _note_router_call() -> None:
+    global _router_calls
+    _router_calls += 1
+
+
 def _refusal(self, hidden_states, top_k_index, top_k_weights):
     """Why this call cannot run on the kernels (None: it can)."""
     from transformers.integrations.moe import _default_apply_gate

@@ -792,6 +792,40 @@ register("moe_experts", _moe_experts_fake, _moe_experts_backward, _moe_experts_s
 register("moe_experts_decode", lambda x, top_k_index, top_k_weights, gate_up, down: x.new_empty(x.shape[0], x.shape[1]))
 
 
+# The router in front of them (MixtralTopKRouter.forward / Qwen3MoeTopKRouter.forward behind their gate product; csrc/moe_router.inc):
+# softmax over the experts, the top_k largest, optional renormalisation -- one launch; the backward recomputes the softmax from
+# the logits and the indices (include/tamd.h tamd_moe_router_bwd).  The indices are not differentiable.
+def _moe_router_fake(logits, top_k, norm, weights_fp32):
+    t = logits.shape[0]
+    return (logits.new_empty(t, top_k, dtype=torch.float32 if weights_fp32 else logits.dtype),
+            logits.new_empty(t, top_k, dtype=torch.int64))
+
+
+def _moe_router_setup(ctx, inputs, output):
+    logits, _top_k, norm, _fp32 = inputs
+    ctx.save_for_backward(logits, output[1])
+    ctx.norm = norm
+    ctx.set_materialize_grads(False)  # (the int64 indices are not differentiable: autograd passes None for them)
+
+
+def _moe_router_backward(ctx, dweights, _dindices):
+    if dweights is None:
+        return None, None, None, None
+    logits, indices = ctx.saved_tensors
+    return T.moe_router_bwd(dweights, logits, indices, ctx.norm), None, None, None
+
+
+def _moe_router_bwd_fake(dweights, logits, indices, norm):
+    # the real op keeps the logits' row stride: a [:, :E] view of a wider product gets a [:, :E] view of a [T, lde] buffer
+    t, e = logits.shape
+    lde = logits.stride(0) if (logits.stride(1) == 1 and logits.stride(0) >= e) else e
+    return logits.new_empty(t, lde)[:, :e] if lde != e else logits.new_empty(t, e)
+
+
+register("moe_router_bwd", _moe_router_bwd_fake)
+register("moe_router", _moe_router_fake, _moe_router_backward, _moe_router_setup)
+
+
 def _bias_act_setup(ctx, inputs, output):
     ctx.save_for_backward(inputs[0], inputs[1])
     ctx.act = inputs[2]
@@ -1073,6 +1107,16 @@ def moe_experts(x, top_k_index, top_k_weights, gate_up_proj, down_proj):
         _moe_decode_calls += 1
         return T.moe_experts_decode(x, top_k_index, top_k_weights, gate_up_proj, down_proj)
     return T.moe_experts(x, top_k_index, top_k_weights, gate_up_proj, down_proj, train)[0]
+
+
+ROUTER_MAX_TOP_K = 16  # (include/tamd.h tamd_moe_router_fwd)
+
+
+def moe_router(logits, top_k, norm=True, weights_fp32=False):
+    """The router behind the gate product: logits [T, E] (bf16 / fp16, unit column stride, any row stride >= E) ->
+    (weights [T, top_k] in fp32 or the logits' dtype, indices int64 [T, top_k]), ordered as torch.topk(sorted=True); ties go
+    to the lower id (include/tamd.h tamd_moe_router_fwd)."""
+    return T.moe_router(logits, int(top_k), bool(norm), bool(weights_fp32))
 
 
 def bias_act(x, bias, act):

@@ -16,17 +16,45 @@ from torch import nn
 from . import attention, experts
 
 
-def _tables() -> Dict[Type[nn.Module], Type[nn.Module]]:
+def _tables(moe_router: bool = True) -> Dict[Type[nn.Module], Type[nn.Module]]:
     from .models import bert, clip, common, gpt2, llama
 
     table: Dict[Type[nn.Module], Type[nn.Module]] = {}
     for mod in (common, llama, bert, clip, gpt2):
         table.update(mod.REPLACEMENTS)
+    moe = _moe() if moe_router else None
+    if moe is not None:
+        table.update(moe.REPLACEMENTS)
     return table
 
 
+_MOE_MISSING = False
+
+
+def _moe():
+    """models/moe.py, or None -- said once -- with a reference that lacks one of the four sparse-MoE model families it
+    subclasses.  Only those four imports are guarded: an error inside the project's own module is raised."""
+    global _MOE_MISSING
+    import importlib
+
+    for family in ("mixtral", "qwen2_moe", "qwen3_moe", "olmoe"):
+        try:
+            importlib.import_module(f"transformers.models.{family}.modeling_{family}")
+        except ImportError as e:
+            if not _MOE_MISSING:
+                import warnings
+
+                warnings.warn(f"transformers_amd.accelerate: the reference has no {family} model ({e}); the MoE routers stay "
+                              "the reference's")
+                _MOE_MISSING = True
+            return None
+    from .models import moe
+
+    return moe
+
+
 def accelerate(model: nn.Module, attn_implementation: bool = True, fuse_loss: bool = True,
-               fused_lm_head_loss: bool = False, experts_implementation: bool = True) -> nn.Module:
+               fused_lm_head_loss: bool = False, experts_implementation: bool = True, moe_router: bool = True) -> nn.Module:
     """Switch `model` (any PreTrainedModel containing Llama / BERT / CLIP / GPT-2 blocks) to the MI355X path.
 
     * registers and selects `attn_implementation="tamd"` (reference API: `set_attn_implementation`,
@@ -34,7 +62,8 @@ def accelerate(model: nn.Module, attn_implementation: bool = True, fuse_loss: bo
     * on a sparse mixture-of-experts model (one whose experts sit behind `@use_experts_implementation`) registers and selects
       `experts_implementation="tamd"` (reference API: `set_experts_implementation`, modeling_utils.py); `revert` restores
       what `get_experts_implementation()` returned before;
-    * swaps norm / MLP / attention / layer modules for their tamd subclasses in place;
+    * swaps norm / MLP / attention / layer modules for their tamd subclasses in place, and -- unless `moe_router=False` (the
+      A/B switch) -- the softmax + top-k routers of Mixtral / Qwen2-MoE / Qwen3-MoE / OLMoE blocks (models/moe.py);
     * installs the fused cross-entropy as `model.loss_function` for causal-LM heads
       (reference hook: modeling_utils.py:4652-4669);
     * `fused_lm_head_loss=True` (opt-in, Llama): training forwards with labels run the lm_head GEMM and the loss chunk by
@@ -43,13 +72,16 @@ def accelerate(model: nn.Module, attn_implementation: bool = True, fuse_loss: bo
     """
     attention.register()
     experts.register()
-    table = _tables()
+    table = _tables(moe_router)
     n = 0
     for m in model.modules():
         repl = table.get(type(m))
         if repl is not None:
             m.__class__ = repl
             n += 1
+    if moe_router and _moe() is not None:
+        n += _moe().swap_router_subclasses(model)
+        n += _moe().swap_shared_expert_gates(model)
     model._tamd_swapped = n
     if n > 0:  # the unchanged Trainer builds DDP without bucket views and registers no hook: ddp.install_trainer_dropin
         from . import ddp
@@ -134,6 +166,8 @@ class _LossDispatch:
 def revert(model: nn.Module) -> nn.Module:
     """Undo `accelerate` (class swaps only; fused weight storage stays valid for the reference modules)."""
     inv = {v: k for k, v in _tables().items()}
+    if _moe() is not None:
+        _moe().restore(model)  # generated router subclasses, shared-expert gates, cached padded gate weights
     for m in model.modules():
         orig = inv.get(type(m))
         if orig is not None:
