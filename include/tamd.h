@@ -429,6 +429,60 @@ int tamd_moe_router_fwd(const void* logits, void* w, int64_t* top_k_index, int64
 int tamd_moe_router_bwd(const void* logits, const int64_t* top_k_index, const void* dw, void* dlogits, int64_t tokens,
                         int64_t experts, int64_t top_k, int64_t lde, int norm, int w_dtype, int dtype, tamd_stream_t stream);
 
+/* The sigmoid, group-limited router of DeepSeek-V3 and its copies (DeepseekV3TopkRouter.forward,
+ * models/deepseek_v3/modeling_deepseek_v3.py:144-169; Glm4MoeTopkRouter.forward is the same text).  Three entries, additive
+ * under ABI 13.
+ *
+ * The gate product with an fp32 result (:145-147, `F.linear(hidden_states.type(torch.float32), self.weight.type(torch.float32))`):
+ *     logits[t, e] = sum_h f32(x[t, h]) * f32(w[e, h])
+ * x [tokens, hidden] with row stride ldx, w [experts, hidden] contiguous, both in `dtype` (bf16 / f16); logits fp32 with row
+ * stride lde >= experts.  fp32 accumulation (the matrix pipe's), stored UNROUNDED.  A 16-bit x 16-bit product is exact in
+ * fp32, so the result differs from the reference's fp32 F.linear in the ORDER of the summation alone; that order is a function
+ * of (tokens <= 16, hidden) only: the waves of a workgroup split hidden into contiguous runs of 32-element steps and their
+ * partial sums are added in ascending order -- no atomics, nothing that depends on scheduling.  The weight is never converted
+ * or copied.  Two kernels behind one entry: tokens <= 16 streams w once (8 expert rows per workgroup, 16 waves over hidden),
+ * above that 32 tokens x 64 experts per workgroup (8 waves over hidden).
+ * experts <= 256, experts % 8 == 0, hidden % 64 == 0, hidden < 2^22, ldx >= hidden, 1 <= tokens < 2^31: TAMD_E_SHAPE otherwise; x and w
+ * 16-byte aligned with ldx % 8 == 0, logits 4-byte aligned: TAMD_E_ALIGN otherwise. */
+int tamd_moe_gate_f32(const void* x, const void* w, float* logits, int64_t tokens, int64_t experts, int64_t hidden,
+                      int64_t ldx, int64_t lde, int dtype, tamd_stream_t stream);
+/* The selection behind it (:149-169: sigmoid, `+ e_score_correction_bias`, the groups' top-2 sums, topk of the groups,
+ * masked_fill, topk(sorted=False), gather, the renormalisation, `* routed_scaling_factor`).  One launch, one wave per token, no
+ * LDS, no atomics.  logits fp32 [tokens, experts] (row stride lde); bias fp32 [experts] or NULL (zeros); w fp32 [tokens,
+ * top_k]; top_k_index int64 [tokens, top_k].  Per token:
+ *     s_e  = 1 / (1 + exp(-l_e))                  fp32: expf, one addition, one IEEE division; saturates to 0 / 1, never NaN
+ *                                                 for a finite l_e
+ *     c_e  = s_e + b_e                            fp32; a NaN c_e counts as -inf for every choice below
+ *     G    = experts / n_group;  group(e) = e / G
+ *     n_group > 1:  gs_g = (largest c in g) + (second largest c in g);  chosen groups: the topk_group largest by (gs
+ *                   descending, g ascending)  (a NaN gs counts as -inf)
+ *     n_group == 1: every expert is eligible, no group work is done
+ *     e_0 .. e_{k-1}: the k largest by (c descending, e ascending) among the experts of the chosen groups
+ *     norm != 0:   d = (sum_j s_{e_j}, j ascending) + 1e-20f;   w_j = r32(r32(s_{e_j} / d) * scale)
+ *     norm == 0:   w_j = r32(s_{e_j} * scale)
+ *     w[t, j] = w_j;   top_k_index[t, j] = e_j
+ * The pairs are emitted c-descending; the reference's topk(sorted=False) leaves their order unspecified.  tamd_moe_combine sums
+ * j ascending, so the order reaches the model's bits.  The bias steers the choice and never the weight.
+ * experts <= 256, experts % n_group == 0, n_group <= 64, 1 <= topk_group <= n_group, G >= 2 when n_group > 1 (the reference's
+ * topk(2) raises otherwise), 1 <= top_k <= min(16, topk_group * G), lde >= experts, 1 <= tokens < 2^31: TAMD_E_SHAPE otherwise. */
+int tamd_moe_router_group_fwd(const float* logits, const float* bias, float* w, int64_t* top_k_index, int64_t tokens,
+                              int64_t experts, int64_t top_k, int64_t n_group, int64_t topk_group, int64_t lde, int norm,
+                              float scale, tamd_stream_t stream);
+/* Its backward: dlogits fp32 [tokens, experts] (row stride lde) from the same logits, the forward's top_k_index and dw fp32
+ * [tokens, top_k].  s and d are recomputed exactly as the forward computes them.  The bias has no gradient (a buffer, and it
+ * enters the non-differentiable choice alone).  s_j = s_{e_j}, g_j = dw[t, j]:
+ *     norm != 0:  q = sum_j r32(g_j * r32(s_j / d))  (j ascending);   ds_j = (scale / d) * (g_j - q)
+ *     norm == 0:  ds_j = scale * g_j
+ *     dl_{e_j} = (ds_j * s_j) * (1 - s_j);    dl_e = +0 for every unselected e;   columns experts .. lde - 1 written as zeros
+ * An id outside [0, experts) in top_k_index is skipped (in d and q too) and never indexes memory.  The same bounds.
+ * The op over these entries (torch.ops.tamd.moe_gate_logits) rounds the fp32 dlogits ONCE to the operands' type before the
+ * two products of the gate's backward (dX = dl . W, dW = dl^T . X) run on the GEMM kernels; the reference runs both products in
+ * fp32 and rounds their results.  That one rounding moves dX[t, h] by at most 2^-9 sum_e |dl[t, e] w[e, h]| (bf16; 2^-12 for
+ * f16), and dW likewise over the tokens. */
+int tamd_moe_router_group_bwd(const float* logits, const int64_t* top_k_index, const float* dw, float* dlogits, int64_t tokens,
+                              int64_t experts, int64_t top_k, int64_t n_group, int64_t topk_group, int64_t lde, int norm,
+                              float scale, tamd_stream_t stream);
+
 /* ------------------------------------------------------------------ attention (MFMA, flash-style) */
 
 /* Scaled-dot-product attention replacing eager_attention_forward / repeat_kv

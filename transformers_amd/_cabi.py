@@ -104,6 +104,9 @@ SIGNATURES = {
     "tamd_moe_gemv_down": (c_int, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, c_int, c_int, P]),
     "tamd_moe_router_fwd": (c_int, [P, P, P, I64, I64, I64, I64, c_int, c_int, c_int, P]),
     "tamd_moe_router_bwd": (c_int, [P, P, P, P, I64, I64, I64, I64, c_int, c_int, c_int, P]),
+    "tamd_moe_gate_f32": (c_int, [P, P, P, I64, I64, I64, I64, I64, c_int, P]),
+    "tamd_moe_router_group_fwd": (c_int, [P, P, P, P, I64, I64, I64, I64, I64, I64, c_int, c_float, P]),
+    "tamd_moe_router_group_bwd": (c_int, [P, P, P, P, I64, I64, I64, I64, I64, I64, c_int, c_float, P]),
     "tamd_dropout_hash":(ctypes.c_uint32, [ctypes.c_uint64, ctypes.c_uint64]),
     "tamd_attn_dropout_field": (ctypes.c_uint32, [ctypes.c_uint64] * 6),
     "tamd_attn_fwd": (c_int, [POINTER(AttnParams), P]),

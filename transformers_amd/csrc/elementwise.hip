@@ -952,3 +952,7 @@ int tamd_cross_entropy_bwd(const void* logits, const int64_t* labels, const floa
 #include "moe_route.inc"
 // the router in front of them: softmax + top-k, forward and backward (tamd_moe_router_fwd / _bwd)
 #include "moe_router.inc"
+// the sigmoid routers' gate product with an fp32 result (tamd_moe_gate_f32)
+#include "moe_gate.inc"
+// ... and their group-limited selection, forward and backward (tamd_moe_router_group_fwd / _bwd)
+#include "moe_router_group.inc"

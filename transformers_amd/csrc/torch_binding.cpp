@@ -46,7 +46,8 @@ using OptTensor = std::optional<at::Tensor>;
   X(tamd_gemm_swiglu) X(tamd_gemm_swiglu_bwd) X(tamd_gemm_colscale) X(tamd_gemm_seg) X(tamd_gemm_group_workspace_bytes) X(tamd_gemm_group) X(tamd_attn_fwd) X(tamd_attn_bwd)   \
   X(tamd_attn_decode_workspace_bytes) X(tamd_attn_decode) X(tamd_attn_fwd_window) X(tamd_attn_decode_window)          \
   X(tamd_moe_route_workspace_bytes) X(tamd_moe_route) X(tamd_moe_gather) X(tamd_moe_combine) X(tamd_moe_combine_bwd) \
-  X(tamd_gemm_routed) X(tamd_moe_gemv_swiglu) X(tamd_moe_gemv_down) X(tamd_moe_router_fwd) X(tamd_moe_router_bwd)
+  X(tamd_gemm_routed) X(tamd_moe_gemv_swiglu) X(tamd_moe_gemv_down) X(tamd_moe_router_fwd) X(tamd_moe_router_bwd)       \
+  X(tamd_moe_gate_f32) X(tamd_moe_router_group_fwd) X(tamd_moe_router_group_bwd)
 
 struct Api {
   void* handle = nullptr;
@@ -1103,6 +1104,72 @@ Tensor op_moe_router_bwd(const Tensor& dweights, const Tensor& logits, const Ten
   return lde == e ? full : full.narrow(1, 0, e);
 }
 
+// The sigmoid, group-limited routers (csrc/moe_gate.inc, csrc/moe_router_group.inc; DeepseekV3TopkRouter.forward,
+// models/deepseek_v3/modeling_deepseek_v3.py:144-169).  The gate product: x [T, H], w [E, H] in bf16 / fp16 -> fp32 logits [T, E].
+Tensor op_moe_gate_logits(const Tensor& x, const Tensor& w) {
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && (x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf) &&
+                  w.scalar_type() == x.scalar_type() && x.size(1) == w.size(1),
+              "tamd: moe_gate_logits takes x [tokens, hidden] and w [experts, hidden], both bf16 or both fp16");
+  const int64_t t = x.size(0), e = w.size(0), h = w.size(1);
+  TORCH_CHECK(t >= 1 && e >= 8 && e <= 256 && e % 8 == 0 && h % 64 == 0,
+              "tamd: moe_gate_logits takes tokens >= 1, experts <= 256 in multiples of 8 and hidden in multiples of 64");
+  const bool strided = x.stride(1) == 1 && x.stride(0) >= h && x.stride(0) % 8 == 0 && (x.storage_offset() % 8) == 0;
+  const Tensor xc = strided ? x : x.contiguous();
+  const Tensor wc = contig(w);
+  Tensor logits = at::empty({t, e}, x.options().dtype(at::kFloat));
+  Launch L({&xc, &wc});
+  check(api().tamd_moe_gate_f32(ptr(xc), ptr(wc), (float*)mptr(logits), t, e, h, xc.stride(0), e, code_of(xc), L.stream),
+        "tamd_moe_gate_f32");
+  return logits;
+}
+// The selection: fp32 logits [T, E] (unit column stride, row stride >= E), bias fp32 [E] or nothing -> (weights fp32 [T, k],
+// indices int64 [T, k]).  One launch.
+void group_router_checks(const Tensor& lg, int64_t top_k, int64_t n_group, int64_t topk_group) {
+  const int64_t e = lg.size(1);
+  TORCH_CHECK(lg.size(0) >= 1 && e >= 1 && e <= 256 && n_group >= 1 && n_group <= 64 && e % n_group == 0 && topk_group >= 1 &&
+                  topk_group <= n_group && (n_group == 1 || e / n_group >= 2) && top_k >= 1 && top_k <= 16 &&
+                  top_k <= topk_group * (e / n_group),
+              "tamd: moe_router_grouped takes experts <= 256 in n_group <= 64 groups of at least 2, 1 <= topk_group <= n_group "
+              "and 1 <= top_k <= min(16, topk_group * experts / n_group)");
+}
+std::tuple<Tensor, Tensor> op_moe_router_grouped(const Tensor& logits, const OptTensor& bias, int64_t top_k, int64_t n_group,
+                                                 int64_t topk_group, bool norm, double scale) {
+  TORCH_CHECK(logits.dim() == 2 && logits.scalar_type() == at::kFloat, "tamd: moe_router_grouped takes fp32 logits [tokens, experts]");
+  const Tensor lg = router_strided(logits) ? logits : logits.contiguous();
+  group_router_checks(lg, top_k, n_group, topk_group);
+  const int64_t t = lg.size(0), e = lg.size(1);
+  Tensor b;
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == e && bias->scalar_type() == at::kFloat,
+                "tamd: moe_router_grouped takes an fp32 bias [experts]");
+    b = contig(*bias);
+  }
+  Tensor w = at::empty({t, top_k}, lg.options());
+  Tensor idx = at::empty({t, top_k}, lg.options().dtype(at::kLong));
+  Launch L({&lg, &b});
+  check(api().tamd_moe_router_group_fwd((const float*)ptr(lg), (const float*)ptr(b), (float*)mptr(w), (int64_t*)mptr(idx), t, e,
+                                        top_k, n_group, topk_group, lg.stride(0), norm ? 1 : 0, (float)scale, L.stream),
+        "tamd_moe_router_group_fwd");
+  return {w, idx};
+}
+// -> dlogits fp32 [T, E]: the [:, :E] part of a [T, lde] buffer with the logits' row stride (its columns behind E are zeros)
+Tensor op_moe_router_grouped_bwd(const Tensor& dweights, const Tensor& logits, const Tensor& indices, int64_t n_group,
+                                 int64_t topk_group, bool norm, double scale) {
+  TORCH_CHECK(logits.dim() == 2 && logits.scalar_type() == at::kFloat && indices.dim() == 2 && indices.scalar_type() == at::kLong &&
+                  indices.size(0) == logits.size(0) && dweights.sizes() == indices.sizes() && dweights.scalar_type() == at::kFloat,
+              "tamd: moe_router_grouped_bwd takes fp32 logits [T, E], indices (int64) and fp32 dweights [T, k]");
+  const Tensor lg = router_strided(logits) ? logits : logits.contiguous();
+  group_router_checks(lg, indices.size(1), n_group, topk_group);
+  const Tensor idx = contig(indices), dw = contig(dweights);
+  const int64_t t = lg.size(0), e = lg.size(1), lde = lg.stride(0);
+  Tensor full = at::empty({t, lde}, lg.options());
+  Launch L({&lg, &idx, &dw});
+  check(api().tamd_moe_router_group_bwd((const float*)ptr(lg), (const int64_t*)ptr(idx), (const float*)ptr(dw), (float*)mptr(full), t,
+                                        e, idx.size(1), n_group, topk_group, lde, norm ? 1 : 0, (float)scale, L.stream),
+        "tamd_moe_router_group_bwd");
+  return lde == e ? full : full.narrow(1, 0, e);
+}
+
 // kernel-level ops (tests, tools): outputs are the caller's buffers
 void op_moe_route_out(Tensor& count, Tensor& offset, Tensor& pos, Tensor& tiles, const Tensor& idx, int64_t experts) {
   k_moe_route(idx, experts, count, offset, pos, tiles);
@@ -2002,6 +2069,9 @@ TORCH_LIBRARY(tamd, m) {
         "Tensor tiles, Tensor xs, Tensor gus, Tensor acts, Tensor ys) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("moe_router(Tensor logits, int top_k, bool norm, bool weights_fp32) -> (Tensor, Tensor)");
   m.def("moe_router_bwd(Tensor dweights, Tensor logits, Tensor indices, bool norm) -> Tensor");
+  m.def("moe_gate_logits(Tensor x, Tensor w) -> Tensor");
+  m.def("moe_router_grouped(Tensor logits, Tensor? bias, int top_k, int n_group, int topk_group, bool norm, float scale) -> (Tensor, Tensor)");
+  m.def("moe_router_grouped_bwd(Tensor dweights, Tensor logits, Tensor indices, int n_group, int topk_group, bool norm, float scale) -> Tensor");
   m.def("swiglu(Tensor gu) -> Tensor");
   m.def("bias_act(Tensor x, Tensor? bias, int act) -> Tensor");
   m.def("embedding(Tensor ids, Tensor table, int padding_idx=-1) -> Tensor");
@@ -2080,6 +2150,9 @@ TORCH_LIBRARY(tamd, m) {
   m.impl("moe_experts_decode", &op_moe_experts_decode);              \
   m.impl("moe_router", &op_moe_router);                              \
   m.impl("moe_router_bwd", &op_moe_router_bwd);                      \
+  m.impl("moe_gate_logits", &op_moe_gate_logits);                    \
+  m.impl("moe_router_grouped", &op_moe_router_grouped);              \
+  m.impl("moe_router_grouped_bwd", &op_moe_router_grouped_bwd);      \
   m.impl("gemm_swiglu", &op_gemm_swiglu);                            \
   m.impl("gemm_swiglu_bwd", &k_gemm_swiglu_bwd);                     \
   m.impl("attn_fwd", &op_attn_fwd);                                  \

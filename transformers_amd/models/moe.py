@@ -14,10 +14,18 @@ reads the [:, :E] part of that product through its row stride.
 What the kernels do not take (fp32 modules, CPU tensors, more than 256 experts, top_k > 16, a hidden size that is not a
 multiple of 8, a subclass that overrides `forward`) calls the reference's forward -- the subclass's own -- and is counted
 (`transformers_amd.fallback_calls()`); it is never approximated.
-Routers of another form (sigmoid / grouped selection, top-k before softmax, nn.Linear subclasses) are not in the table
-and stay the reference's.
+
+The sigmoid, group-limited routers (DeepseekV3TopkRouter.forward, models/deepseek_v3/modeling_deepseek_v3.py:144-169, and
+every class of the reference whose `forward` is that text: GROUPED below) run `ops.moe_gate_logits` -- the gate product with
+its fp32 accumulators kept, no fp32 copy of the weight -- and ONE launch of `ops.moe_router_grouped` in place of close to
+twenty.  They return the reference's triple: fp32 logits, fp32 weights, int64 indices; the pairs come ordered by sigmoid + bias
+descending where the reference's `topk(sorted=False)` leaves the order open.
+Routers of another form (top-k before softmax, MiniMax-M2's, nn.Linear subclasses) are not in the table and stay the
+reference's.
 """
 from __future__ import annotations
+
+import importlib
 
 import torch
 import torch.nn.functional as F
@@ -100,6 +108,80 @@ REPLACEMENTS = {MixtralTopKRouter: TamdMixtralTopKRouter, Qwen2MoeTopKRouter: Ta
                 Qwen3MoeTopKRouter: TamdQwen3MoeTopKRouter, OlmoeTopKRouter: TamdOlmoeTopKRouter}
 
 
+# ---- the sigmoid, group-limited routers ------------------------------------------------------------------------------
+# Every router class of the reference whose `forward` source is textually DeepseekV3TopkRouter.forward
+# (tests/test_moe_router_group_models.py asserts the identity for each class of the table, so an upgrade of the reference that
+# changes one of them fails loudly).  A family the installed reference lacks is left out.
+GROUPED = (("deepseek_v3", "DeepseekV3TopkRouter"), ("deepseek_v32", "DeepseekV32TopkRouter"), ("glm4_moe", "Glm4MoeTopkRouter"),
+           ("glm4_moe_lite", "Glm4MoeLiteTopkRouter"), ("glm4v_moe", "Glm4vMoeTextTopkRouter"), ("glm_moe_dsa", "GlmMoeDsaTopkRouter"),
+           ("dots1", "Dots1TopkRouter"), ("solar_open", "SolarOpenTopkRouter"), ("exaone_moe", "ExaoneMoeTopkRouter"),
+           ("axk1", "AXK1TopkRouter"), ("mimo_v2_flash", "MiMoV2FlashTopkRouter"), ("nemotron_h", "NemotronHTopkRouter"))
+
+
+def _grouped_refusal(self, hidden_states):
+    """Why this call cannot run on the kernels (None: it can): the bounds of include/tamd.h tamd_moe_gate_f32 /
+    tamd_moe_router_group_fwd."""
+    w = self.weight
+    if not torch.is_tensor(hidden_states) or not _gpu(hidden_states) or hidden_states.device != w.device:
+        return "device"
+    if hidden_states.dtype not in (torch.bfloat16, torch.float16) or w.dtype != hidden_states.dtype:
+        return "dtype"
+    e, h = w.shape
+    if e > experts.MAX_EXPERTS or e % 8:
+        return "experts"
+    ng, tg = self.num_group, self.topk_group
+    if not (1 <= ng <= ops.ROUTER_MAX_GROUPS and e % ng == 0 and 1 <= tg <= ng and (ng == 1 or e // ng >= 2)):
+        return "groups"
+    if not 1 <= self.top_k <= min(ops.ROUTER_MAX_TOP_K, tg * (e // ng)):
+        return "top_k"
+    if h % ops.GATE_HIDDEN_MULTIPLE or hidden_states.shape[-1] != h or hidden_states.numel() == 0 or self.num_experts != e:
+        return "shape"
+    return None
+
+
+def _fp32_bias(self):
+    """`e_score_correction_bias` as the kernel takes it: fp32.  `model.bfloat16()` turns the buffer into bf16 (only
+    `from_pretrained` keeps it fp32); bf16 -> fp32 is exact, and the converted copy is cached like the padded gate weight."""
+    b = self.e_score_correction_bias
+    if b.dtype == torch.float32:
+        return b
+    key = (b.data_ptr(), b._version, b.dtype, b.device)
+    cached = self.__dict__.get("_tamd_fp32_bias")
+    if cached is None or cached[0] != key:
+        cached = (key, b.detach().float())
+        self.__dict__["_tamd_fp32_bias"] = cached
+    return cached[1]
+
+
+def _grouped_forward(self, reference, hidden_states):
+    why = _grouped_refusal(self, hidden_states)
+    if why is not None:
+        note_fallback(self, hidden_states, why)
+        return reference.forward(self, hidden_states)
+    x = hidden_states.reshape(-1, self.hidden_dim)
+    router_logits = ops.moe_gate_logits(x, self.weight)
+    weights, indices = ops.moe_router_grouped(router_logits, _fp32_bias(self), self.top_k, self.num_group, self.topk_group,
+                                              bool(self.norm_topk_prob), float(self.routed_scaling_factor))
+    experts._note_router_call()
+    return router_logits, weights, indices
+
+
+def _grouped_replacement(reference):
+    def forward(self, hidden_states):
+        return _grouped_forward(self, reference, hidden_states)
+    return type("Tamd" + reference.__name__, (reference,), {"forward": forward, "__module__": __name__})
+
+
+GROUPED_REPLACEMENTS = {}
+for _family, _name in GROUPED:
+    try:
+        _cls = getattr(importlib.import_module(f"transformers.models.{_family}.modeling_{_family}"), _name)
+    except (ImportError, AttributeError):
+        continue
+    GROUPED_REPLACEMENTS[_cls] = globals()["Tamd" + _name] = _grouped_replacement(_cls)
+REPLACEMENTS.update(GROUPED_REPLACEMENTS)
+
+
 class TamdSharedExpertGate(TamdLinear):
     """Qwen2MoeSparseMoeBlock.shared_expert_gate, nn.Linear(hidden, 1, bias=False) (models/qwen2_moe/modeling_qwen2_moe.py: the
     sigmoid gate of the shared expert): one output row, which the GEMM's row stores do not take -- the product runs over the
@@ -114,7 +196,7 @@ class TamdSharedExpertGate(TamdLinear):
         return super().forward(x)
 
 
-# A subclass of one of the four router classes is not in the exact-class table.  One that keeps the reference's `forward` gets
+# A subclass of one of the router classes is not in the exact-class table.  One that keeps the reference's `forward` gets
 # the kernels like its parent; one that overrides `forward` computes something this package does not know: its own forward
 # runs, counted under "subclass_forward".  Either way the module becomes a generated subclass of ITS class, which remembers
 # the class it replaced for `revert`.
@@ -157,6 +239,7 @@ def restore(model) -> None:
         elif type(m) is TamdSharedExpertGate:
             m.__class__ = torch.nn.Linear
         m.__dict__.pop("_tamd_padded_gate", None)
+        m.__dict__.pop("_tamd_fp32_bias", None)
 
 
 def swap_shared_expert_gates(model) -> int:

@@ -826,6 +826,53 @@ register("moe_router_bwd", _moe_router_bwd_fake)
 register("moe_router", _moe_router_fake, _moe_router_backward, _moe_router_setup)
 
 
+# The sigmoid, group-limited routers (DeepseekV3TopkRouter.forward, models/deepseek_v3/modeling_deepseek_v3.py:144-169;
+# csrc/moe_gate.inc, csrc/moe_router_group.inc).  The gate product keeps its fp32 accumulators (include/tamd.h tamd_moe_gate_f32).
+# Its backward receives the fp32 gradient of the logits -- the router's plus whatever a caller added through the returned
+# router_logits -- rounds it ONCE to the operands' type and runs the two products on the GEMM kernels (dX = dl . W, dW = dl^T . X);
+# the reference runs them in fp32.  (include/tamd.h tamd_moe_router_group_bwd states the bound of that rounding.)
+def _moe_gate_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+
+
+def _moe_gate_backward(ctx, dlogits):
+    x, w = ctx.saved_tensors
+    dl = dlogits.to(x.dtype)
+    dx = T.gemm(dl, w, False, True) if ctx.needs_input_grad[0] else None
+    dw = T.gemm(dl, _c(x), True, True) if ctx.needs_input_grad[1] else None
+    return dx, dw
+
+
+register("moe_gate_logits", lambda x, w: x.new_empty(x.shape[0], w.shape[0], dtype=torch.float32), _moe_gate_backward,
+         _moe_gate_setup)
+
+
+def _moe_router_grouped_fake(logits, bias, top_k, n_group, topk_group, norm, scale):
+    t = logits.shape[0]
+    return logits.new_empty(t, top_k), logits.new_empty(t, top_k, dtype=torch.int64)
+
+
+def _moe_router_grouped_setup(ctx, inputs, output):
+    logits, _bias, _top_k, ctx.n_group, ctx.topk_group, ctx.norm, ctx.scale = inputs
+    ctx.save_for_backward(logits, output[1])
+    ctx.set_materialize_grads(False)
+
+
+def _moe_router_grouped_backward(ctx, dweights, _dindices):
+    if dweights is None:
+        return (None,) * 7
+    logits, indices = ctx.saved_tensors
+    return (T.moe_router_grouped_bwd(dweights, logits, indices, ctx.n_group, ctx.topk_group, ctx.norm, ctx.scale),) + (None,) * 6
+
+
+def _moe_router_grouped_bwd_fake(dweights, logits, indices, n_group, topk_group, norm, scale):
+    return _moe_router_bwd_fake(dweights, logits, indices, norm)
+
+
+register("moe_router_grouped_bwd", _moe_router_grouped_bwd_fake)
+register("moe_router_grouped", _moe_router_grouped_fake, _moe_router_grouped_backward, _moe_router_grouped_setup)
+
+
 def _bias_act_setup(ctx, inputs, output):
     ctx.save_for_backward(inputs[0], inputs[1])
     ctx.act = inputs[2]
@@ -1117,6 +1164,22 @@ def moe_router(logits, top_k, norm=True, weights_fp32=False):
     (weights [T, top_k] in fp32 or the logits' dtype, indices int64 [T, top_k]), ordered as torch.topk(sorted=True); ties go
     to the lower id (include/tamd.h tamd_moe_router_fwd)."""
     return T.moe_router(logits, int(top_k), bool(norm), bool(weights_fp32))
+
+
+GATE_HIDDEN_MULTIPLE = 64  # (include/tamd.h tamd_moe_gate_f32)
+ROUTER_MAX_GROUPS = 64     # (include/tamd.h tamd_moe_router_group_fwd)
+
+
+def moe_gate_logits(x, w):
+    """The gate product of the sigmoid routers: x [T, H], w [E, H], both bf16 or both fp16 -> fp32 logits [T, E], the fp32
+    accumulators unrounded (include/tamd.h tamd_moe_gate_f32).  E <= 256 in multiples of 8, H in multiples of 64."""
+    return T.moe_gate_logits(x, w)
+
+
+def moe_router_grouped(logits, bias, top_k, n_group=1, topk_group=1, norm=True, scale=1.0):
+    """The sigmoid, group-limited selection: fp32 logits [T, E], fp32 bias [E] or None -> (weights fp32 [T, top_k], indices
+    int64 [T, top_k]), ordered by sigmoid + bias descending; ties go to the lower id (include/tamd.h tamd_moe_router_group_fwd)."""
+    return T.moe_router_grouped(logits, bias, int(top_k), int(n_group), int(topk_group), bool(norm), float(scale))
 
 
 def bias_act(x, bias, act):

@@ -63,7 +63,8 @@ def accelerate(model: nn.Module, attn_implementation: bool = True, fuse_loss: bo
       `experts_implementation="tamd"` (reference API: `set_experts_implementation`, modeling_utils.py); `revert` restores
       what `get_experts_implementation()` returned before;
     * swaps norm / MLP / attention / layer modules for their tamd subclasses in place, and -- unless `moe_router=False` (the
-      A/B switch) -- the softmax + top-k routers of Mixtral / Qwen2-MoE / Qwen3-MoE / OLMoE blocks (models/moe.py);
+      A/B switch) -- the softmax + top-k routers of Mixtral / Qwen2-MoE / Qwen3-MoE / OLMoE blocks and the sigmoid, group-limited
+      routers of DeepSeek-V3 / GLM-4-MoE and their copies (models/moe.py);
     * installs the fused cross-entropy as `model.loss_function` for causal-LM heads
       (reference hook: modeling_utils.py:4652-4669);
     * `fused_lm_head_loss=True` (opt-in, Llama): training forwards with labels run the lm_head GEMM and the loss chunk by
