@@ -93,7 +93,8 @@ __global__ __launch_bounds__(kAttnThreads, (DROP && D > 64) ? 1 : ((D == 64 && !
     const int last = qw0 + 31 < a.seq_q ? qw0 + 31 : a.seq_q - 1;
     klo_min = window_klo(a, CAUSAL ? qw0 + off : seq_k - 1);
     klo_max = window_klo(a, CAUSAL ? last + off : seq_k - 1);
-    klo = CAUSAL ? window_klo(a, qrow + off) : klo_min;  // (without the causal mask: one bound for all rows)
+    // (a row behind seq_q takes bound 0, as under the planes: it cannot trigger a rescale of the live rows)
+    klo =CAUSAL ? (qrow < a.seq_q ? window_klo(a, qrow + off) : 0) : klo_min;  // (without the causal mask: one bound for all rows)
     // the lane's bound is ONE register from here on, as the plane's value is in the other instantiations (left transparent, the
     // mask arithmetic of the 32 elements was rewritten around row + off - W and hoisted out of the tile loop: scratch,
     // profiles/attn_window_isa.md)
