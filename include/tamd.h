@@ -591,6 +591,24 @@ int tamd_attn_fwd_window(const struct tamd_attn_params* p, int64_t window, tamd_
 int tamd_attn_decode_window(const struct tamd_attn_params* p, int64_t window, void* workspace, size_t workspace_bytes,
                             tamd_stream_t stream); /* workspace: tamd_attn_decode_workspace_bytes(p) */
 
+/* Added under ABI 13: new entry points, tamd_attn_params unchanged.  Forward attention whose QK^T depth differs from its PV
+ * width: MULTI-HEAD LATENT ATTENTION as the reference's DeepSeek-V2 / -V3 / Moonlight family hands it to the attention interface
+ * (models/deepseek_v3/modeling_deepseek_v3.py DeepseekV3Attention.forward: query_states / key_states = cat(nope 128, rotary
+ * 64) -> [B, H, S, 192], value_states [B, H, S, 128] straight out of kv_b_proj, scaling from yarn_apply_mscale).
+ *   p->head_dim is the width of the q and k rows; the v and o rows are head_dim_v wide.  Every stride is in elements, as above;
+ *   v may be a strided view of the fused kv_b_proj output (head stride 256, column offset 128).
+ * Accepted: (head_dim, head_dim_v) == (192, 128); anything else is TAMD_E_SHAPE.  bf16 / fp16, grouped-query heads as above.
+ * Query row s sees key k iff  k <= s + (seq_k - seq_q)  (causal; any seq_q <= seq_k: a KV cache)  and key_valid (when given)
+ * allows it.  A row without a visible key: O = 0, lse = +inf.  tamd_attn_decode_mla is the split-KV schedule of tamd_attn_decode
+ * for few query rows over a long key range (workspace: tamd_attn_decode_mla_workspace_bytes(p, head_dim_v), 16-byte aligned).
+ * Inference only (there is no backward).  TAMD_E_ARG for: dropout_p != 0; q_start != NULL; seq_k_dev != NULL; seq_q > seq_k.
+ * Every other check is that of tamd_attn_fwd, with head_dim_v in the row-stride bounds of v and o.  A refused call writes
+ * nothing.  tamd_attn_fwd / tamd_attn_decode / tamd_attn_bwd keep refusing head_dim 192. */
+int tamd_attn_fwd_mla(const struct tamd_attn_params* p, int64_t head_dim_v, tamd_stream_t stream);
+size_t tamd_attn_decode_mla_workspace_bytes(const struct tamd_attn_params* p, int64_t head_dim_v);
+int tamd_attn_decode_mla(const struct tamd_attn_params* p, int64_t head_dim_v, void* workspace, size_t workspace_bytes,
+                         tamd_stream_t stream);
+
 /* Backward (SURVEY §8a "Attention"): delta = rowsum(dO*O); dV = P^T dO; dS = P*(dP - delta);
  * dQ = scale dS K; dK = scale dS^T Q; GQA sums dK/dV over the query heads of a group. */
 struct tamd_attn_bwd_params {

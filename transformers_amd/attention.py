@@ -401,8 +401,10 @@ def tamd_attention_forward(module, query, key, value, attention_mask, dropout: f
         raise TamdError("attn_implementation='tamd' needs GPU tensors (no CPU fallback); use 'eager' or 'sdpa' on CPU")
     b, hq, sq, d = query.shape
     sk = key.shape[2]
-    if d not in (64, 128):
-        raise TamdError(f"attn_implementation='tamd' supports head_dim 64 and 128, got {d}")
+    mla = (d, value.shape[-1]) == (192, 128)  # multi-head latent attention as the reference expands it (DeepSeek-V2 / -V3)
+    if not mla and (d not in (64, 128) or value.shape[-1] != d):
+        raise TamdError(f"attn_implementation='tamd' supports head_dim 64 and 128, got {d}" +
+                        ("" if value.shape[-1] == d else f" (value head_dim {value.shape[-1]}; of the unequal pairs: 192 / 128)"))
     if query.dtype == torch.float32 and torch.is_autocast_enabled():
         # mixed precision with fp32 master weights (Trainer(bf16=True)): the projections ran in the autocast dtype but
         # cos/sin are fp32, so q/k arrive in fp32 after the rotary -- autocast would cast them for torch's own attention
@@ -424,6 +426,21 @@ def tamd_attention_forward(module, query, key, value, attention_mask, dropout: f
         sk = used  # pre-allocated cache: only the first kv_len key slots are in use (strided views of the cache)
         k, v = k[:, :sk], v[:, :sk]
     window = attention_mask.window if isinstance(attention_mask, TamdMask) else None
+    if mla:
+        # the MLA kernel (csrc/attention_mla_kernel.inc): causal with the bottom-right diagonal over a DynamicCache, a padding
+        # mask; everything else is named and refused, never computed with another mask
+        key_valid, q_start, kv_len = split_mask_kv(attention_mask, b, sk)
+        sw = kwargs.get("sliding_window")
+        refused = [name for name, hit in (
+            ("attention dropout", bool(drop_p)), ("cu_seq_lens (a flattened batch)", kwargs.get("cu_seq_lens_q") is not None),
+            ("packed sequences", q_start is not None), ("a sliding window", window is not None or (sw is not None and int(sw) < sk)),
+            ("key counts in device memory (cache_implementation=\"static\")", kv_len is not None or (used is not None and used != key.shape[2])),
+            ("more queries than keys", sq > sk)) if hit]
+        if refused:
+            raise TamdError("attn_implementation='tamd': MLA attention (head dims 192 / 128) does not take " + ", ".join(refused) +
+                            "; use 'sdpa' or 'eager'")
+        q, k, v = (t if t.stride(3) == 1 else t.contiguous() for t in (q, k, v))
+        return ops.attention(q, k, v, float(scaling), causal, key_valid), None
     if window is not None:
         # a multi-token step over a sliding-window cache (tamd_mask): K / V are the L keys the cache returned, the bound is
         # computed in the kernel -- no planes, and the `sliding_window` keyword below says nothing more

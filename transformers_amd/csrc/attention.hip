@@ -27,6 +27,7 @@
 namespace tamd {
 
 #include "attention_fwd_kernel.inc"
+#include "attention_mla_kernel.inc"
 
 }  // namespace tamd
 
@@ -106,6 +107,34 @@ int attn_decode_launch(const AttnArgs& a, bool causal, hipStream_t s) {
 #undef TAMD_AD
   const int rows = a.batch * a.seq_q * a.heads_q;
   hipLaunchKernelGGL((attn_combine_kernel<T, D>), dim3((unsigned)rows), dim3(256), 0, s, a);  // one workgroup per row
+  return launch_status();
+}
+
+// MLA (attention_mla_kernel.inc: q / k 192 wide, v / o 128): 80 KB of dynamic LDS, above what a kernel is granted unasked
+template <typename T, bool CAUSAL, bool SPLIT>
+void attn_mla_launch_one(const AttnArgs& a, unsigned blocks, hipStream_t s) {
+#if defined(__HIP__)
+  static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mla_kernel<T, CAUSAL, SPLIT>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kMlaSmem);
+  (void)raised;  // (a refusal shows as the launch's error)
+#endif
+  hipLaunchKernelGGL((attn_mla_kernel<T, CAUSAL, SPLIT>), dim3(blocks), dim3(kAttnThreads), (size_t)kMlaSmem, s, a);
+}
+template <typename T>
+int attn_mla_launch(const AttnArgs& a, bool causal, bool split, hipStream_t s) {
+  const unsigned blocks = (unsigned)(a.nqt * a.heads_q * a.batch * a.kv_splits);
+  if (split) {
+    if (causal)
+      attn_mla_launch_one<T, true, true>(a, blocks, s);
+    else
+      attn_mla_launch_one<T, false, true>(a, blocks, s);
+    const int rows = a.batch * a.seq_q * a.heads_q;
+    hipLaunchKernelGGL((attn_combine_kernel<T, kMlaDv>), dim3((unsigned)rows), dim3(256), 0, s, a);  // one workgroup per row
+  } else if (causal) {
+    attn_mla_launch_one<T, true, false>(a, blocks, s);
+  } else {
+    attn_mla_launch_one<T, false, false>(a, blocks, s);
+  }
   return launch_status();
 }
 
@@ -325,6 +354,50 @@ extern "C" int tamd_attn_decode_window(const struct tamd_attn_params* p, int64_t
   const int chk = attn_window_check(p, window);
   if (chk != TAMD_OK) return chk;
   return attn_decode_run(p, window, workspace, workspace_bytes, stream);
+}
+
+// ---- multi-head latent attention as the reference expands it (models/deepseek_v3/modeling_deepseek_v3.py
+// DeepseekV3Attention.forward): q / k rows of p->head_dim = 192, v / o rows of head_dim_v = 128.  Inference only.
+static int attn_mla_check(const tamd_attn_params* p, int64_t head_dim_v) {
+  if (!p) return TAMD_E_NULL;
+  if (p->head_dim != kMlaDqk || head_dim_v != kMlaDv) return TAMD_E_SHAPE;
+  tamd_attn_params c = *p;
+  c.head_dim = head_dim_v;  // the v / o rows, and every check that does not depend on the width
+  const int chk = attn_check(&c);
+  if (chk != TAMD_OK) return chk;
+  if ((p->seq_q > 1 && p->q_stride_s < p->head_dim) || (p->seq_k > 1 && p->k_stride_s < p->head_dim)) return TAMD_E_ARG;
+  if (p->dropout_p != 0.f || p->q_start != nullptr || p->seq_k_dev != nullptr || p->seq_q > p->seq_k) return TAMD_E_ARG;
+  return TAMD_OK;
+}
+extern "C" int tamd_attn_fwd_mla(const struct tamd_attn_params* p, int64_t head_dim_v, tamd_stream_t stream) {
+  const int chk = attn_mla_check(p, head_dim_v);
+  if (chk != TAMD_OK) return chk;
+  const AttnArgs a = make_args(p);
+  TAMD_DISPATCH_HALF(p->dtype, return attn_mla_launch<T>(a, p->causal != 0, false, TAMD_STREAM(stream)));
+  return TAMD_E_DTYPE;
+}
+extern "C" size_t tamd_attn_decode_mla_workspace_bytes(const struct tamd_attn_params* p, int64_t head_dim_v) {
+  if (!p || head_dim_v <= 0) return 0;
+  tamd_attn_params c = *p;
+  c.head_dim = head_dim_v;  // the partial rows are output rows
+  return tamd_attn_decode_workspace_bytes(&c);
+}
+extern "C" int tamd_attn_decode_mla(const struct tamd_attn_params* p0, int64_t head_dim_v, void* workspace,
+                                    size_t workspace_bytes, tamd_stream_t stream) {
+  const int chk = attn_mla_check(p0, head_dim_v);
+  if (chk != TAMD_OK) return chk;
+  if (!workspace) return TAMD_E_NULL;
+  if (workspace_bytes < tamd_attn_decode_mla_workspace_bytes(p0, head_dim_v) || !aligned16(workspace)) return TAMD_E_WORKSPACE;
+  const DecodePlan d = decode_plan(p0);  // (the plan follows rows, heads and keys, not the widths)
+  AttnArgs a = make_args(&d.p);
+  a.xcd_map = 0;
+  a.kv_splits = d.splits;
+  a.tiles_per_split = d.tiles_per_split;
+  const size_t rows = (size_t)d.splits * (size_t)d.p.batch * (size_t)d.p.seq_q * (size_t)d.p.heads_q;
+  a.o_part = reinterpret_cast<float*>(workspace);
+  a.lse_part = a.o_part + rows * (size_t)kMlaDv;
+  TAMD_DISPATCH_HALF(d.p.dtype, return attn_mla_launch<T>(a, d.p.causal != 0, true, TAMD_STREAM(stream)));
+  return TAMD_E_DTYPE;
 }
 
 extern "C" int tamd_attn_bwd(const struct tamd_attn_bwd_params* p, tamd_stream_t stream) {

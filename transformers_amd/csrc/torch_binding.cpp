@@ -45,6 +45,7 @@ using OptTensor = std::optional<at::Tensor>;
   X(tamd_cross_entropy_fwd) X(tamd_cross_entropy_bwd) X(tamd_gemm) X(tamd_gemm_workspace_bytes) X(tamd_gemm_ws)       \
   X(tamd_gemm_swiglu) X(tamd_gemm_swiglu_bwd) X(tamd_gemm_colscale) X(tamd_gemm_seg) X(tamd_gemm_group_workspace_bytes) X(tamd_gemm_group) X(tamd_attn_fwd) X(tamd_attn_bwd)   \
   X(tamd_attn_decode_workspace_bytes) X(tamd_attn_decode) X(tamd_attn_fwd_window) X(tamd_attn_decode_window)          \
+  X(tamd_attn_fwd_mla) X(tamd_attn_decode_mla_workspace_bytes) X(tamd_attn_decode_mla)                                  \
   X(tamd_moe_route_workspace_bytes) X(tamd_moe_route) X(tamd_moe_gather) X(tamd_moe_combine) X(tamd_moe_combine_bwd) \
   X(tamd_gemm_routed) X(tamd_moe_gemv_swiglu) X(tamd_moe_gemv_down) X(tamd_moe_router_fwd) X(tamd_moe_router_bwd)       \
   X(tamd_moe_gate_f32) X(tamd_moe_router_group_fwd) X(tamd_moe_router_group_bwd)
@@ -1385,6 +1386,27 @@ std::tuple<Tensor, Tensor> k_attn_window(const Tensor& q, const Tensor& k, const
   return {o, lse};
 }
 
+// multi-head latent attention as the reference expands it (include/tamd.h tamd_attn_fwd_mla / tamd_attn_decode_mla): q / k rows
+// of 192, v rows of 128 -> o [B,Sq,Hq,128].  Inference only; the schedule is picked by the rule above
+std::tuple<Tensor, Tensor> k_attn_mla(const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal,
+                                      const OptTensor& key_valid_, bool need_lse) {
+  Launch L({&q, &k, &v, p(key_valid_)});
+  const int64_t dv = v.size(3);
+  Tensor o = at::empty({q.size(0), q.size(1), q.size(2), dv}, q.options());
+  Tensor lse = need_lse ? f32_like(q, {q.size(0), q.size(2), q.size(1)}) : Tensor();
+  Tensor key_valid = checked_key_valid(key_valid_, q, k);
+  tamd_attn_params ap{};
+  fill_attn_params(&ap, q, k, v, o, lse, key_valid, scale, causal, 0.0, 0, Tensor());
+  if (kDecodeKernel && q.size(1) <= kDecodeMaxRows && k.size(1) >= kDecodeMinKeys) {
+    const size_t nbytes = api().tamd_attn_decode_mla_workspace_bytes(&ap, dv);
+    Tensor ws = at::empty({(int64_t)nbytes}, q.options().dtype(at::kByte));
+    check(api().tamd_attn_decode_mla(&ap, dv, mptr(ws), nbytes, L.stream), "tamd_attn_decode_mla");
+    return {o, lse};
+  }
+  check(api().tamd_attn_fwd_mla(&ap, dv, L.stream), "tamd_attn_fwd_mla");
+  return {o, lse};
+}
+
 // gradients written into dq / dk / dv (views with the strides of q / k / v) or freshly allocated.  rope = (cos, sin): q and k
 // had been rotated before the attention, dq and dk leave through the transposed rotation.
 std::tuple<Tensor, Tensor, Tensor> k_attn_bwd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
@@ -1536,6 +1558,12 @@ std::tuple<Tensor, Tensor> op_attn_window(const Tensor& q_, const Tensor& k_, co
                                           const OptTensor& key_valid, int64_t window, bool need_lse) {
   const Tensor q = attn_operand(q_), k = attn_operand(k_), v = attn_operand(v_);
   auto [o, lse] = k_attn_window(q, k, v, scale, causal, key_valid, window, need_lse);
+  return {o, lse.defined() ? lse : nothing(q)};
+}
+std::tuple<Tensor, Tensor> op_attn_mla(const Tensor& q_, const Tensor& k_, const Tensor& v_, double scale, bool causal,
+                                       const OptTensor& key_valid, bool need_lse) {
+  const Tensor q = attn_operand(q_), k = attn_operand(k_), v = attn_operand(v_);
+  auto [o, lse] = k_attn_mla(q, k, v, scale, causal, key_valid, need_lse);
   return {o, lse.defined() ? lse : nothing(q)};
 }
 std::tuple<Tensor, Tensor, Tensor> op_attn_bwd(const Tensor& q_, const Tensor& k_, const Tensor& v_, const Tensor& o_,
@@ -2038,6 +2066,8 @@ TORCH_LIBRARY(tamd, m) {
         "float dropout_p=0.0, int seed=0, Tensor? q_start=None, Tensor? seed_dev=None, Tensor? kv_len=None) -> (Tensor, Tensor)");
   m.def("attn_window(Tensor q, Tensor k, Tensor v, float scale, bool causal, Tensor? key_valid, int window, "
         "bool need_lse=True) -> (Tensor, Tensor)");
+  m.def("attn_mla(Tensor q, Tensor k, Tensor v, float scale, bool causal, Tensor? key_valid=None, bool need_lse=True) -> "
+        "(Tensor, Tensor)");
   m.def("attn_bwd(Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor dout, float scale, bool causal, "
         "Tensor? key_valid=None, float dropout_p=0.0, int seed=0, Tensor? q_start=None, Tensor? rope_cos=None, "
         "Tensor? rope_sin=None, Tensor? seed_dev=None) -> (Tensor, Tensor, Tensor)");
@@ -2157,6 +2187,7 @@ TORCH_LIBRARY(tamd, m) {
   m.impl("gemm_swiglu_bwd", &k_gemm_swiglu_bwd);                     \
   m.impl("attn_fwd", &op_attn_fwd);                                  \
   m.impl("attn_window", &op_attn_window);                            \
+  m.impl("attn_mla", &op_attn_mla);                                  \
   m.impl("attn_bwd", &op_attn_bwd);                                  \
   m.impl("attn_bwd_out", &op_attn_bwd_out);                          \
   m.impl("rmsnorm", &op_rmsnorm);                                    \

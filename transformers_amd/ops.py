@@ -305,13 +305,28 @@ def _check_window(window, dropout_p, q_start, kv_len) -> int:
     return int(window)
 
 
+def _check_mla(q, k, v, dropout_p, q_start, kv_len, window) -> None:
+    if _wants_grad(q, k, v):
+        raise TamdError("MLA attention (192 / 128 head dims) has no backward on the kernels yet: for training select "
+                        "attn_implementation=\"sdpa\"")
+    if dropout_p or q_start is not None or kv_len is not None or window is not None:
+        raise TamdError("MLA attention (value rows narrower than query rows: 192 / 128) is an inference path: it takes no "
+                        "dropout, no packed-sequence bounds, no key counts in device memory and no sliding window")
+
+
 def raw_attn_fwd(q, k, v, scale, causal, key_valid=None, need_lse=True, dropout_p=0.0, seed=0, q_start=None, seed_dev=None,
                  kv_len=None, window=None):
     """q [B,Sq,Hq,D], k/v [B,Sk,Hkv,D] (strided views fine) -> o [B,Sq,Hq,D] contiguous, lse [B,Hq,Sq] fp32.
     kv_len (int32 [B] on the device, or None): the key slots in use per batch row -- k / v are a pre-allocated cache, row b is
     computed as if they had been sliced to kv_len[b] rows (include/tamd.h seq_k_dev; always the split-KV decode kernel).
     window (int or None): a causal sliding window over a KV cache -- query s sees the keys s + off - window + 1 .. s + off,
-    off = Sk - Sq (include/tamd.h tamd_attn_fwd_window / tamd_attn_decode_window, picked by the shape like the plain call)."""
+    off = Sk - Sq (include/tamd.h tamd_attn_fwd_window / tamd_attn_decode_window, picked by the shape like the plain call).
+    v narrower than q (multi-head latent attention: q / k [.., 192], v [.., 128]) -> o [B,Sq,Hq,128] from the MLA kernel
+    (include/tamd.h tamd_attn_fwd_mla / tamd_attn_decode_mla)."""
+    if v.shape[-1] != q.shape[-1]:
+        _check_mla(q, k, v, dropout_p, q_start, kv_len, window)
+        o, lse = T.attn_mla(q, k, v, float(scale), bool(causal), key_valid, need_lse)
+        return o, (lse if need_lse else None)
     if window is not None:
         o, lse = T.attn_window(q, k, v, float(scale), bool(causal), key_valid, _check_window(window, dropout_p, q_start, kv_len),
                                need_lse)
@@ -504,6 +519,8 @@ register("attn_fwd", lambda q, k, v, scale, causal, key_valid=None, need_lse=Tru
     q.new_empty(q.shape), _f32(q, q.shape[0], q.shape[2], q.shape[1]) if need_lse else _nothing(q)))
 register("attn_window", lambda q, k, v, scale, causal, key_valid, window, need_lse=True: (
     q.new_empty(q.shape), _f32(q, q.shape[0], q.shape[2], q.shape[1]) if need_lse else _nothing(q)))
+register("attn_mla", lambda q, k, v, scale, causal, key_valid=None, need_lse=True: (
+    q.new_empty(*q.shape[:3], v.shape[3]), _f32(q, q.shape[0], q.shape[2], q.shape[1]) if need_lse else _nothing(q)))
 register("attn_bwd", lambda q, k, v, o, lse, dout, scale, causal, key_valid=None, dropout_p=0.0, seed=0, q_start=None,
          rope_cos=None, rope_sin=None, seed_dev=None: (
              torch.empty_strided(q.shape, q.stride(), dtype=q.dtype, device=q.device),
@@ -1263,6 +1280,9 @@ def attention(q, k, v, scale, causal, key_valid=None, dropout_p=0.0, seed=None, 
     if dropout_p > 0.0 and seed is None and seed_dev is None:
         (seed,), seed_dev = dropout_seeds(1, q.device)
     train = _wants_grad(q, k, v)
+    if v.shape[-1] != q.shape[-1]:
+        _check_mla(q, k, v, dropout_p, q_start, kv_len, window)
+        return T.attn_mla(q, k, v, float(scale), bool(causal), key_valid, False)[0]
     if window is not None:
         window = _check_window(window, dropout_p, q_start, kv_len)
         if train:
