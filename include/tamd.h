@@ -498,7 +498,11 @@ int tamd_moe_router_group_bwd(const float* logits, const int64_t* top_k_index, c
  * causal: key k visible to query s iff k <= s + (seq_k - seq_q)  (masking_utils.py:76-81).
  * key_valid: optional [batch, seq_k] uint8 padding mask (1 = attend); NULL = no padding.
  * lse [batch, heads_q, seq_q] fp32 (natural-log sum-exp of the scaled scores) is written for
- * the backward; may be NULL for inference.  head_dim in {64, 128}; bf16/f16. */
+ * the backward; may be NULL for inference.  head_dim in {64, 128}; bf16/f16.
+ * head_dim 256 (Gemma: csrc/attention_d256_kernel.inc) is accepted by tamd_attn_fwd and tamd_attn_decode /
+ * tamd_attn_decode_workspace_bytes alone, as an inference path: causal with the offset above for seq_q <= seq_k, key_valid,
+ * grouped-query heads.  At 256, TAMD_E_ARG for dropout_p != 0, q_start != NULL, seq_k_dev != NULL and seq_q > seq_k;
+ * tamd_attn_fwd_window, tamd_attn_decode_window and tamd_attn_bwd keep returning TAMD_E_SHAPE.  A refused call writes nothing. */
 /* 32-bit mixing function of the dropout masks (exported so hosts/tests can rebuild them). */
 uint32_t tamd_dropout_hash(uint64_t seed, uint64_t index);
 /* ABI 7: the 16-bit field that decides attention-dropout element (batch_head = b*heads_q + h, q, k): one hash decides a
@@ -566,7 +570,7 @@ int tamd_attn_fwd(const struct tamd_attn_params* p, tamd_stream_t stream);
  * any seq_q), different schedule: with one query row
  * and grouped-query attention the query heads of a KV head share one pass over its keys, and the key range is split over
  * enough workgroups to fill the GPU (split-KV; fp32 partial rows in `workspace`, merged by a second kernel).
- * workspace: tamd_attn_decode_workspace_bytes(p) bytes, 16-byte aligned. */
+ * workspace: tamd_attn_decode_workspace_bytes(p) bytes, 16-byte aligned (it follows head_dim: 64, 128 or 256). */
 size_t tamd_attn_decode_workspace_bytes(const struct tamd_attn_params* p);
 int tamd_attn_decode(const struct tamd_attn_params* p, void* workspace, size_t workspace_bytes, tamd_stream_t stream);
 

@@ -399,11 +399,14 @@ def tamd_attention_forward(module, query, key, value, attention_mask, dropout: f
         raise TamdError(f"attention dropout must be in [0, 1), got {drop_p}")
     if not query.is_cuda and ops.backend().name == "hip":
         raise TamdError("attn_implementation='tamd' needs GPU tensors (no CPU fallback); use 'eager' or 'sdpa' on CPU")
+    if kwargs.get("softcap"):  # (Gemma-2's attn_logit_softcapping: tanh(s / cap) * cap on the scores, in front of the mask)
+        raise TamdError(f"attn_implementation='tamd': logit soft-capping (softcap={kwargs['softcap']}) is not implemented in the "
+                        "attention kernels, and is never dropped silently; use 'eager' or 'sdpa'")
     b, hq, sq, d = query.shape
     sk = key.shape[2]
     mla = (d, value.shape[-1]) == (192, 128)  # multi-head latent attention as the reference expands it (DeepSeek-V2 / -V3)
-    if not mla and (d not in (64, 128) or value.shape[-1] != d):
-        raise TamdError(f"attn_implementation='tamd' supports head_dim 64 and 128, got {d}" +
+    if not mla and (d not in (64, 128, 256) or value.shape[-1] != d):
+        raise TamdError(f"attn_implementation='tamd' supports head_dim 64, 128 and 256, got {d}" +
                         ("" if value.shape[-1] == d else f" (value head_dim {value.shape[-1]}; of the unequal pairs: 192 / 128)"))
     if query.dtype == torch.float32 and torch.is_autocast_enabled():
         # mixed precision with fp32 master weights (Trainer(bf16=True)): the projections ran in the autocast dtype but
@@ -438,6 +441,23 @@ def tamd_attention_forward(module, query, key, value, attention_mask, dropout: f
             ("more queries than keys", sq > sk)) if hit]
         if refused:
             raise TamdError("attn_implementation='tamd': MLA attention (head dims 192 / 128) does not take " + ", ".join(refused) +
+                            "; use 'sdpa' or 'eager'")
+        q, k, v = (t if t.stride(3) == 1 else t.contiguous() for t in (q, k, v))
+        return ops.attention(q, k, v, float(scaling), causal, key_valid), None
+    if d == 256:
+        # the head_dim-256 kernel (csrc/attention_d256_kernel.inc; Gemma): the same inference path -- a DynamicCache, left
+        # padding, multi-token steps over a cache; a window that does not bind (>= the keys) is plain causal attention, as it is
+        # at 64 / 128; everything else is named and refused
+        key_valid, q_start, kv_len = split_mask_kv(attention_mask, b, sk)
+        sw = kwargs.get("sliding_window")
+        refused = [name for name, hit in (
+            ("attention dropout", bool(drop_p)), ("cu_seq_lens (a flattened batch)", kwargs.get("cu_seq_lens_q") is not None),
+            ("packed sequences", q_start is not None),
+            ("a binding sliding window", (window is not None and int(window) < sk) or (sw is not None and int(sw) < sk)),
+            ("key counts in device memory (cache_implementation=\"static\")", kv_len is not None or (used is not None and used != key.shape[2])),
+            ("more queries than keys", sq > sk)) if hit]
+        if refused:
+            raise TamdError("attn_implementation='tamd': attention at head_dim 256 does not take " + ", ".join(refused) +
                             "; use 'sdpa' or 'eager'")
         q, k, v = (t if t.stride(3) == 1 else t.contiguous() for t in (q, k, v))
         return ops.attention(q, k, v, float(scaling), causal, key_valid), None

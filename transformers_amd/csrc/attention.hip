@@ -28,6 +28,7 @@ namespace tamd {
 
 #include "attention_fwd_kernel.inc"
 #include "attention_mla_kernel.inc"
+#include "attention_d256_kernel.inc"
 
 }  // namespace tamd
 
@@ -138,9 +139,38 @@ int attn_mla_launch(const AttnArgs& a, bool causal, bool split, hipStream_t s) {
   return launch_status();
 }
 
-int attn_check(const tamd_attn_params* p) {
+// head_dim 256 (attention_d256_kernel.inc): 128 KB of dynamic LDS, one workgroup per CU.  `split`: the pieces go to the merge kernel
+template <typename T, bool CAUSAL, bool SPLIT>
+void attn_d256_launch_one(const AttnArgs& a, unsigned blocks, hipStream_t s) {
+#if defined(__HIP__)
+  static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_d256_kernel<T, CAUSAL, SPLIT>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kD256Smem);
+  (void)raised;  // (a refusal shows as the launch's error)
+#endif
+  hipLaunchKernelGGL((attn_d256_kernel<T, CAUSAL, SPLIT>), dim3(blocks), dim3(kAttnThreads), (size_t)kD256Smem, s, a);
+}
+template <typename T>
+int attn_d256_launch(const AttnArgs& a, bool causal, bool split, hipStream_t s) {
+  const unsigned blocks = (unsigned)(a.nqt * a.heads_q * a.batch * a.kv_splits);
+  if (split) {
+    if (causal)
+      attn_d256_launch_one<T, true, true>(a, blocks, s);
+    else
+      attn_d256_launch_one<T, false, true>(a, blocks, s);
+    const int rows = a.batch * a.seq_q * a.heads_q;
+    hipLaunchKernelGGL((attn_combine_kernel<T, kD256>), dim3((unsigned)rows), dim3(256), 0, s, a);  // one workgroup per row
+  } else if (causal) {
+    attn_d256_launch_one<T, true, false>(a, blocks, s);
+  } else {
+    attn_d256_launch_one<T, false, false>(a, blocks, s);
+  }
+  return launch_status();
+}
+
+// wide: the caller has a kernel for head_dim 256 (tamd_attn_fwd, tamd_attn_decode), an inference path with fewer features
+int attn_check(const tamd_attn_params* p, bool wide = false) {
   if (!p || !p->q || !p->k || !p->v || !p->o) return TAMD_E_NULL;
-  if (p->head_dim != 64 && p->head_dim != 128) return TAMD_E_SHAPE;
+  if (p->head_dim != 64 && p->head_dim != 128 && !(wide && p->head_dim == kD256)) return TAMD_E_SHAPE;
   if (p->batch <= 0 || p->heads_q <= 0 || p->heads_kv <= 0 || p->seq_q <= 0 || p->seq_k <= 0) return TAMD_E_SHAPE;
   if (p->heads_q % p->heads_kv != 0) return TAMD_E_SHAPE;
   if (p->dtype != TAMD_BF16 && p->dtype != TAMD_F16) return TAMD_E_DTYPE;
@@ -158,6 +188,9 @@ int attn_check(const tamd_attn_params* p) {
   for (int i = 0; i < 4; ++i)
     if (row_counts[i] > 1 && (row_strides[i] < p->head_dim || row_strides[i] > ((int64_t)1 << 24))) return TAMD_E_ARG;
   if (!aligned16(p->q) || !aligned16(p->k) || !aligned16(p->v) || !aligned16(p->o)) return TAMD_E_ALIGN;
+  if (p->head_dim == kD256 &&
+      (p->dropout_p != 0.f || p->q_start != nullptr || p->seq_k_dev != nullptr || p->seq_q > p->seq_k))
+    return TAMD_E_ARG;
   return TAMD_OK;
 }
 
@@ -236,12 +269,14 @@ extern "C" uint32_t tamd_attn_dropout_field(uint64_t seed, uint64_t batch_head, 
 }
 
 extern "C" int tamd_attn_fwd(const struct tamd_attn_params* p, tamd_stream_t stream) {
-  const int chk = attn_check(p);
+  const int chk = attn_check(p, true);
   if (chk != TAMD_OK) return chk;
   if (p->seq_k_dev != nullptr) return TAMD_E_ARG;  // key counts in device memory: tamd_attn_decode (inference) only
   const AttnArgs a = make_args(p);
   hipStream_t s = TAMD_STREAM(stream);
-  if (p->head_dim == 128) {
+  if (p->head_dim == kD256) {
+    TAMD_DISPATCH_HALF(p->dtype, return attn_d256_launch<T>(a, p->causal != 0, false, s));
+  } else if (p->head_dim == 128) {
     TAMD_DISPATCH_HALF(p->dtype, return (attn_fwd_launch<T, 128>(a, p->causal != 0, s)));
   } else {
     TAMD_DISPATCH_HALF(p->dtype, return (attn_fwd_launch<T, 64>(a, p->causal != 0, s)));
@@ -310,7 +345,9 @@ static int attn_decode_run(const tamd_attn_params* p0, int64_t window, void* wor
   a.o_part = reinterpret_cast<float*>(workspace);
   a.lse_part = a.o_part + rows * (size_t)d.p.head_dim;
   hipStream_t s = TAMD_STREAM(stream);
-  if (d.p.head_dim == 128) {
+  if (d.p.head_dim == kD256) {  // (never with a window or key counts: attn_check)
+    TAMD_DISPATCH_HALF(d.p.dtype, return attn_d256_launch<T>(a, d.p.causal != 0, true, s));
+  } else if (d.p.head_dim == 128) {
     TAMD_DISPATCH_HALF(d.p.dtype, return (attn_decode_launch<T, 128>(a, d.p.causal != 0, s)));
   } else {
     TAMD_DISPATCH_HALF(d.p.dtype, return (attn_decode_launch<T, 64>(a, d.p.causal != 0, s)));
@@ -319,7 +356,7 @@ static int attn_decode_run(const tamd_attn_params* p0, int64_t window, void* wor
 }
 extern "C" int tamd_attn_decode(const struct tamd_attn_params* p0, void* workspace, size_t workspace_bytes,
                                 tamd_stream_t stream) {
-  const int chk = attn_check(p0);
+  const int chk = attn_check(p0, true);
   if (chk != TAMD_OK) return chk;
   if (p0->dropout_p != 0.f || p0->q_start != nullptr) return TAMD_E_ARG;  // (with or without seq_k_dev)
   return attn_decode_run(p0, 0, workspace, workspace_bytes, stream);

@@ -1340,7 +1340,8 @@ Tensor checked_kv_len(const OptTensor& kv_len, const Tensor& q) {
   return contig(*kv_len);
 }
 
-// q [B,Sq,Hq,D], k/v [B,Sk,Hkv,D] (strided views fine) -> o [B,Sq,Hq,D] contiguous, lse [B,Hq,Sq] fp32 or undefined
+// q [B,Sq,Hq,D], k/v [B,Sk,Hkv,D] (strided views fine) -> o [B,Sq,Hq,D] contiguous, lse [B,Hq,Sq] fp32 or undefined.
+// D = 256 (include/tamd.h: an inference path) takes the same two entry points and the same schedule rule
 std::tuple<Tensor, Tensor> k_attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal,
                                       const OptTensor& key_valid_, bool need_lse, double dropout_p, int64_t seed,
                                       const OptTensor& q_start_, bool q_prescaled = false,

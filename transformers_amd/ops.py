@@ -314,6 +314,17 @@ def _check_mla(q, k, v, dropout_p, q_start, kv_len, window) -> None:
                         "dropout, no packed-sequence bounds, no key counts in device memory and no sliding window")
 
 
+def _check_d256(q, k, v, dropout_p, q_start, kv_len, window) -> None:
+    if _wants_grad(q, k, v):
+        raise TamdError("attention at head_dim 256 has no backward on the kernels yet: for training select "
+                        "attn_implementation=\"sdpa\"")
+    refused = [name for name, hit in (("dropout", bool(dropout_p)), ("packed-sequence bounds", q_start is not None),
+                                      ("key counts in device memory", kv_len is not None),
+                                      ("a binding sliding window", window is not None and int(window) < k.shape[1])) if hit]
+    if refused:
+        raise TamdError("attention at head_dim 256 is an inference path: it takes no " + ", no ".join(refused))
+
+
 def raw_attn_fwd(q, k, v, scale, causal, key_valid=None, need_lse=True, dropout_p=0.0, seed=0, q_start=None, seed_dev=None,
                  kv_len=None, window=None):
     """q [B,Sq,Hq,D], k/v [B,Sk,Hkv,D] (strided views fine) -> o [B,Sq,Hq,D] contiguous, lse [B,Hq,Sq] fp32.
@@ -322,11 +333,15 @@ def raw_attn_fwd(q, k, v, scale, causal, key_valid=None, need_lse=True, dropout_
     window (int or None): a causal sliding window over a KV cache -- query s sees the keys s + off - window + 1 .. s + off,
     off = Sk - Sq (include/tamd.h tamd_attn_fwd_window / tamd_attn_decode_window, picked by the shape like the plain call).
     v narrower than q (multi-head latent attention: q / k [.., 192], v [.., 128]) -> o [B,Sq,Hq,128] from the MLA kernel
-    (include/tamd.h tamd_attn_fwd_mla / tamd_attn_decode_mla)."""
+    (include/tamd.h tamd_attn_fwd_mla / tamd_attn_decode_mla).
+    D = 256 (Gemma): the same entry points on the head_dim-256 kernel -- inference only, key_valid the one optional operand."""
     if v.shape[-1] != q.shape[-1]:
         _check_mla(q, k, v, dropout_p, q_start, kv_len, window)
         o, lse = T.attn_mla(q, k, v, float(scale), bool(causal), key_valid, need_lse)
         return o, (lse if need_lse else None)
+    if q.shape[-1] == 256:  # (csrc/attention_d256_kernel.inc; a window that does not bind is the plain call)
+        _check_d256(q, k, v, dropout_p, q_start, kv_len, window)
+        window = None
     if window is not None:
         o, lse = T.attn_window(q, k, v, float(scale), bool(causal), key_valid, _check_window(window, dropout_p, q_start, kv_len),
                                need_lse)
@@ -1283,6 +1298,9 @@ def attention(q, k, v, scale, causal, key_valid=None, dropout_p=0.0, seed=None, 
     if v.shape[-1] != q.shape[-1]:
         _check_mla(q, k, v, dropout_p, q_start, kv_len, window)
         return T.attn_mla(q, k, v, float(scale), bool(causal), key_valid, False)[0]
+    if q.shape[-1] == 256:
+        _check_d256(q, k, v, dropout_p, q_start, kv_len, window)
+        window = None
     if window is not None:
         window = _check_window(window, dropout_p, q_start, kv_len)
         if train:
