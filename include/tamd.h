@@ -397,6 +397,37 @@ int tamd_moe_gemv_down(const void* act, const int64_t* top_k_index, const void* 
                        int64_t tokens, int64_t top_k, int64_t experts, int64_t hidden, int64_t inter, int64_t ldact,
                        int w_dtype, int dtype, tamd_stream_t stream);
 
+/* Linear layers with FP8 block-scaled weights (csrc/gemv_fp8.inc): the dense projections of the DeepSeek-V3 / R1, Qwen3-FP8 and
+ * GLM-FP8 checkpoints as integrations/finegrained_fp8.py FP8Linear holds them.  Additive under ABI 13.  Inference only, W8A16:
+ * the activations are NEVER quantised (the reference's own forward quantises them per 128 values and is further from the exact
+ * product; this is not bit-parity with its Triton kernel), and no FP8 MFMA is used.
+ *   W8   [N, K] bytes (row stride ldw) of OCP e4m3fn: bias 7, subnormals, no infinities, max 448; NaN codes (0x7f, 0xff) are
+ *        not produced by a quantiser and are unspecified here
+ *   S    [ceil(N / 128), ceil(K / 128)] fp32 (row stride lds), the `weight_scale_inv`: one scale per 128 x 128 block of W8
+ *   X    [M, K] (ldx), bias [N] or NULL, R [M, N] (ldr) or NULL, Y [M, N] (ldy) in T = `dtype` (bf16 / f16)
+ *   epilogue TAMD_EPI_NONE / TAMD_EPI_BIAS / TAMD_EPI_RESIDUAL with tamd_gemm's roundings (bias optional under RESIDUAL)
+ * Two forms, chosen by M:
+ *   M <= 16   Y[m, n] = rT( sum_k X[m, k] * (f32(W8[n, k]) * S[n / 128, k / 128]) [+ bias[n]] ), accumulated in fp32; the
+ *             dequantised weight is never rounded to T.  One launch that streams W8 once: HBM traffic N K + 4 |S| + M (K + N)
+ *             sizeof(T) bytes.  (Per lane and step the 16 products of one scale block are summed unscaled and enter the
+ *             accumulator as fma(scale, partial, acc): the result differs from the expression above by fp32 summation error.)
+ *   M  > 16   Wd = rT( r32( f32(W8) * S ) ), then Y = tamd_gemm(X, Wd, bias, R) with that kernel's documented roundings.  Wd is
+ *             built in chunks of whole scale rows inside `workspace`: chunk_bytes caps a chunk (0: 64 MiB; never less than 128
+ *             rows), tamd_gemm_fp8w_workspace_bytes(M, N, K, chunk_bytes) is the size to pass (0 for M <= 16).
+ * The two forms differ by ONE rounding of every weight to T.
+ * Refusals, before any launch and with every output untouched: TAMD_E_DTYPE for any dtype but bf16 / f16; TAMD_E_SHAPE for a
+ * non-positive dimension, K % 16 != 0, a leading dimension below its width, and -- M > 16 only -- N % 8 != 0 or ldy % 8 != 0;
+ * TAMD_E_ARG for a NULL operand, X / W8 not 16-byte aligned or ldx % 8 / ldw % 16 != 0, another epilogue, and -- M > 16 -- Y / R
+ * not 16-byte aligned, a NULL or misaligned workspace or workspace_bytes below the query's answer. */
+size_t tamd_gemm_fp8w_workspace_bytes(int64_t M, int64_t N, int64_t K, size_t chunk_bytes);
+int tamd_gemm_fp8w(const void* X, const void* W8, const float* S, void* Y, const void* bias, const void* R, int64_t M, int64_t N,
+                   int64_t K, int64_t ldx, int64_t ldw, int64_t lds, int64_t ldy, int64_t ldr, int epilogue, int dtype,
+                   void* workspace, size_t workspace_bytes, size_t chunk_bytes, tamd_stream_t stream);
+/* Wd[n, k] = rT( r32( f32(W8[n, k]) * S[n / 128, k / 128] ) ): the dequantisation step of the M > 16 form on its own.  Every
+ * e4m3 value is exact in bf16 and f16.  W8 [N, K] (ldw), Wd [N, K] (ldd, elements, % 8 == 0), 16-byte aligned; K % 16 == 0. */
+int tamd_dequant_fp8w(const void* W8, const float* S, void* Wd, int64_t N, int64_t K, int64_t ldw, int64_t lds, int64_t ldd,
+                      int dtype, tamd_stream_t stream);
+
 /* The router in front of those experts: softmax over the experts, the top_k largest, optional renormalisation -- what follows
  * the gate product in MixtralTopKRouter.forward (models/mixtral/modeling_mixtral.py: `softmax(router_logits, dtype=float)`,
  * `torch.topk`, `router_top_value /= router_top_value.sum(-1, keepdim=True)`) and in Qwen3MoeTopKRouter.forward

@@ -1,0 +1,99 @@
+"""FP8 block-scaled linear (torch.ops.tamd.linear_fp8w: csrc/gemv_fp8.inc) against this project's bf16 product on the same N, K
+(ops.linear: csrc/gemv.hip at M <= 16, the GEMM kernels above) -- the yardstick: the streaming form reads half the bytes -- and,
+with --reference where its Triton path runs on the box, the reference's FP8Linear.forward.  DeepSeek-V3 dense shapes at M = 1, 8, 16, 512.
+
+Every arm walks a ring of weight copies larger than the 256 MB of last-level cache, so each launch streams its weights from HBM;
+the arms alternate inside one process; one JSON line per point, appended to --out when given.  Times are per call (device events
+around a window of calls, launch overhead included), and the TB/s fields are the algorithmic bytes over that per-call time: not
+kernel time.
+
+    python tools/fp8_linear_bench.py [--out profiles/fp8_linear_ab.jsonl]
+"""
+import argparse
+import json
+import sys
+from pathlib import Path
+
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from transformers_amd import ops  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--out", default=None)
+ap.add_argument("--ring-bytes", type=int, default=640 << 20)
+ap.add_argument("--reference", action="store_true",
+                help="also time FP8Linear.forward (its Triton kernel comes from the `kernels` hub package: needs that package and its cache)")
+args = ap.parse_args()
+dev = torch.device("cuda:0")
+SHAPES = [(7168, 1536), (7168, 576), (1536, 24576), (16384, 7168), (7168, 18432), (18432, 7168)]  # K -> N
+ROWS = [1, 8, 16, 512]
+
+
+def timed(fn, iters):
+    st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    st.record()
+    for i in range(iters):
+        fn(i)
+    en.record()
+    torch.cuda.synchronize()
+    return st.elapsed_time(en) / iters
+
+
+def reference_module(w8, s):
+    from transformers.integrations.finegrained_fp8 import FP8Linear
+
+    m = FP8Linear(w8.shape[1], w8.shape[0], block_size=(128, 128)).to(dev)
+    m.weight, m.weight_scale_inv = torch.nn.Parameter(w8, requires_grad=False), torch.nn.Parameter(s, requires_grad=False)
+    return m
+
+
+torch.manual_seed(0)
+# None: not tried yet; a string: why it is not timed; True: runs
+reference_state = None if args.reference else "not requested: its Triton kernel is loaded through the `kernels` hub package"
+for k, n in SHAPES:
+    ring = max(2, min(64, -(-args.ring_bytes // (n * k))))  # the same number of copies for both arms: the bf16 ring is twice the bytes
+    wb = [(torch.randn(n, k, device=dev) * 0.05).bfloat16() for _ in range(ring)]
+    # per-block scales that keep every quotient inside e4m3's range (|w| <= 448 s): the tensor's maximum over 448, times 1 .. 2
+    sc = [(w.abs().max().float() / 448.0) * (1 + torch.rand(-(-n // 128), -(-k // 128), device=dev)) for w in wb]
+    w8 = [(w.float() / s.repeat_interleave(128, 0)[:n].repeat_interleave(128, 1)[:, :k]).to(torch.float8_e4m3fn)
+          for w, s in zip(wb, sc)]
+    for m in ROWS:
+        x = torch.randn(m, k, device=dev).bfloat16()
+        arms = {"fp8w": lambda i: ops.linear_fp8w(x, w8[i % ring], sc[i % ring]),
+                "bf16": lambda i: ops.linear(x, wb[i % ring])}
+        if reference_state in (None, True):
+            mods = [reference_module(w, s) for w, s in zip(w8, sc)]
+            try:
+                with torch.no_grad():
+                    mods[0](x)
+                torch.cuda.synchronize()
+                reference_state = True
+                arms["reference_fp8linear"] = lambda i: mods[i % ring](x)
+            except Exception as e:  # (no Triton kernel for this box: reported, not timed)
+                reference_state = f"{type(e).__name__}: {str(e)[:160]}"
+        with torch.no_grad():
+            y, yb = arms["fp8w"](0).float(), arms["bf16"](0).float()
+            slowest = max(timed(fn, 5) for fn in arms.values())
+            iters = max(10, min(20000, int(250.0 / max(slowest, 1e-3))))  # a timed window of ~250 ms of the slowest arm
+            for fn in arms.values():
+                timed(fn, 3)
+            ms = {a: [] for a in arms}
+            for _ in range(args.rounds):  # alternating
+                for a, fn in arms.items():
+                    ms[a].append(timed(fn, iters))
+        med = {a: sorted(v)[len(v) // 2] for a, v in ms.items()}
+        nbytes = {"fp8w": n * k + 4 * sc[0].numel() + m * (k + n) * 2, "bf16": 2 * n * k + m * (k + n) * 2}
+        rec = {"K": k, "N": n, "M": m, "ring": ring, "iters": iters, "rel_diff_fp8w_vs_bf16_product": round(float((y - yb).norm() / yb.norm()), 4),
+               **{f"{a}_ms": [round(v, 4) for v in ms[a]] for a in arms}, **{f"{a}_median_ms": round(med[a], 4) for a in arms},
+               **{f"{a}_TBps": round(nbytes[a] / (med[a] * 1e-3) / 1e12, 3) for a in nbytes},
+               "fp8w_over_bf16": round(med["fp8w"] / med["bf16"], 3),
+               "reference_fp8linear": "timed" if reference_state is True else f"not run ({reference_state})", "clock_probe": "not run"}
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+    del wb, w8, sc
+    torch.cuda.empty_cache()

@@ -102,6 +102,9 @@ SIGNATURES = {
     "tamd_gemm_routed": (c_int, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, c_int, c_int, c_int, P]),
     "tamd_moe_gemv_swiglu": (c_int, [P, P, P, P, I64, I64, I64, I64, I64, I64, c_int, P]),
     "tamd_moe_gemv_down": (c_int, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, c_int, c_int, P]),
+    "tamd_gemm_fp8w_workspace_bytes": (c_size_t, [I64, I64, I64, c_size_t]),
+    "tamd_gemm_fp8w": (c_int, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, c_int, c_int, P, c_size_t, c_size_t, P]),
+    "tamd_dequant_fp8w": (c_int, [P, P, P, I64, I64, I64, I64, I64, c_int, P]),
     "tamd_moe_router_fwd": (c_int, [P, P, P, I64, I64, I64, I64, c_int, c_int, c_int, P]),
     "tamd_moe_router_bwd": (c_int, [P, P, P, P, I64, I64, I64, I64, c_int, c_int, c_int, P]),
     "tamd_moe_gate_f32": (c_int, [P, P, P, I64, I64, I64, I64, I64, c_int, P]),

@@ -334,3 +334,5 @@ int gemv_run(const GemvArgs& g, int epilogue, int dtype, hipStream_t stream) {
 
 // the experts of a mixture-of-experts block on the same stream (tamd_moe_gemv_swiglu / tamd_moe_gemv_down)
 #include "gemv_moe.inc"
+// FP8 block-scaled weights on the same stream (tamd_gemm_fp8w / tamd_dequant_fp8w)
+#include "gemv_fp8.inc"

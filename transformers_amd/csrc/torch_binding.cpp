@@ -48,7 +48,8 @@ using OptTensor = std::optional<at::Tensor>;
   X(tamd_attn_fwd_mla) X(tamd_attn_decode_mla_workspace_bytes) X(tamd_attn_decode_mla)                                  \
   X(tamd_moe_route_workspace_bytes) X(tamd_moe_route) X(tamd_moe_gather) X(tamd_moe_combine) X(tamd_moe_combine_bwd) \
   X(tamd_gemm_routed) X(tamd_moe_gemv_swiglu) X(tamd_moe_gemv_down) X(tamd_moe_router_fwd) X(tamd_moe_router_bwd)       \
-  X(tamd_moe_gate_f32) X(tamd_moe_router_group_fwd) X(tamd_moe_router_group_bwd)
+  X(tamd_moe_gate_f32) X(tamd_moe_router_group_fwd) X(tamd_moe_router_group_bwd)                                      \
+  X(tamd_gemm_fp8w_workspace_bytes) X(tamd_gemm_fp8w)
 
 struct Api {
   void* handle = nullptr;
@@ -1067,6 +1068,43 @@ Tensor op_moe_experts_decode(const Tensor& x, const Tensor& top_k_index, const T
                                  code_of(w), code_of(x), L.stream),
         "tamd_moe_gemv_down");
   return out;
+}
+
+// nn.Linear over FP8 block-scaled weights (integrations/finegrained_fp8.py FP8Linear.forward; csrc/gemv_fp8.inc): x [.., K] in
+// bf16 / fp16, w8 [N, K] float8_e4m3fn, scale_inv [ceil(N / 128), ceil(K / 128)] fp32, bias [N] or None -> [.., N].  Up to 16
+// rows stream the bytes once; more rows dequantise row chunks into a workspace in front of the GEMM kernels.  Inference only:
+// there is no autograd formula, and an input that requires grad is refused by name.
+Tensor op_linear_fp8w(const Tensor& x, const Tensor& w8, const Tensor& scale_inv, const OptTensor& bias) {
+  if (at::GradMode::is_enabled()) {
+    const char* who = x.requires_grad() ? "x" : w8.requires_grad() ? "w8" : scale_inv.requires_grad() ? "scale_inv" : (bias && bias->requires_grad()) ? "bias" : nullptr;
+    TORCH_CHECK(who == nullptr, "tamd: linear_fp8w is an inference path (no backward on the kernels): `", who,
+                "` requires grad; run under torch.no_grad() or keep the reference's FP8Linear for training");
+  }
+  TORCH_CHECK(x.dim() >= 1 && w8.dim() == 2 && scale_inv.dim() == 2 && x.size(-1) == w8.size(1),
+              "tamd: linear_fp8w takes x [.., K], w8 [N, K] and scale_inv [ceil(N / 128), ceil(K / 128)]");
+  TORCH_CHECK(w8.scalar_type() == at::kFloat8_e4m3fn, "tamd: linear_fp8w takes float8_e4m3fn weights, got ", w8.scalar_type());
+  TORCH_CHECK(scale_inv.scalar_type() == at::kFloat, "tamd: linear_fp8w takes fp32 scales, got ", scale_inv.scalar_type());
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf, "tamd: linear_fp8w takes bf16 / fp16 activations, got ",
+              x.scalar_type());
+  const int64_t n = w8.size(0), k = w8.size(1);
+  TORCH_CHECK(scale_inv.size(0) == (n + 127) / 128 && scale_inv.size(1) == (k + 127) / 128,
+              "tamd: linear_fp8w serves 128 x 128 scale blocks: scale_inv must be [", (n + 127) / 128, ", ", (k + 127) / 128, "]");
+  TORCH_CHECK(!bias || (bias->dim() == 1 && bias->size(0) == n && bias->scalar_type() == x.scalar_type()),
+              "tamd: linear_fp8w: bias must be [N] in the activations' dtype");
+  const Tensor x2 = contig(x).view({-1, k}), w = contig(w8), sc = contig(scale_inv);
+  const Tensor b = bias ? contig(*bias) : Tensor();
+  const int64_t m = x2.size(0);
+  std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
+  shape.back() = n;
+  Tensor y = at::empty({m, n}, x.options());
+  if (m == 0) return y.view(shape);
+  Launch L({&x2, &w, &sc, &b});
+  const size_t nbytes = api().tamd_gemm_fp8w_workspace_bytes(m, n, k, 0);
+  Tensor ws = nbytes ? at::empty({(int64_t)nbytes}, x.options().dtype(at::kByte)) : Tensor();
+  check(api().tamd_gemm_fp8w(ptr(x2), ptr(w), (const float*)ptr(sc), mptr(y), ptr(b), nullptr, m, n, k, k, k, sc.size(1), n, 0,
+                             b.defined() ? TAMD_EPI_BIAS : TAMD_EPI_NONE, code_of(x2), nbytes ? mptr(ws) : nullptr, nbytes, 0, L.stream),
+        "tamd_gemm_fp8w");
+  return y.view(shape);
 }
 
 // The router in front of the experts (csrc/moe_router.inc; MixtralTopKRouter.forward / Qwen3MoeTopKRouter.forward after their
@@ -2098,6 +2136,7 @@ TORCH_LIBRARY(tamd, m) {
   m.def("moe_experts_decode(Tensor x, Tensor top_k_index, Tensor top_k_weights, Tensor gate_up, Tensor down) -> Tensor");
   m.def("moe_experts_bwd(Tensor dout, Tensor top_k_weights, Tensor gate_up, Tensor down, Tensor pos, Tensor count, Tensor offset, "
         "Tensor tiles, Tensor xs, Tensor gus, Tensor acts, Tensor ys) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("linear_fp8w(Tensor x, Tensor w8, Tensor scale_inv, Tensor? bias) -> Tensor");
   m.def("moe_router(Tensor logits, int top_k, bool norm, bool weights_fp32) -> (Tensor, Tensor)");
   m.def("moe_router_bwd(Tensor dweights, Tensor logits, Tensor indices, bool norm) -> Tensor");
   m.def("moe_gate_logits(Tensor x, Tensor w) -> Tensor");
@@ -2179,6 +2218,7 @@ TORCH_LIBRARY(tamd, m) {
   m.impl("moe_experts", &op_moe_experts);                            \
   m.impl("moe_experts_bwd", &op_moe_experts_bwd);                    \
   m.impl("moe_experts_decode", &op_moe_experts_decode);              \
+  m.impl("linear_fp8w", &op_linear_fp8w);                            \
   m.impl("moe_router", &op_moe_router);                              \
   m.impl("moe_router_bwd", &op_moe_router_bwd);                      \
   m.impl("moe_gate_logits", &op_moe_gate_logits);                    \

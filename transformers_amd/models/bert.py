@@ -13,7 +13,7 @@ from transformers.models.bert import modeling_bert as ref
 
 from .. import layer_ops, ops
 from ..fused_params import FusedWeights, PaddedRows
-from .common import _gpu, _has_hooks, _placement_ok, note_fallback
+from .common import _gpu, _has_hooks, _placement_ok, note_fallback, plain_weights
 
 
 def _no_dropout(mod) -> bool:
@@ -34,7 +34,8 @@ class TamdBertSelfAttention(ref.BertSelfAttention):
         d = self.attention_head_size
         if not (_gpu(hidden_states) and past_key_values is None and d in (64, 128)
                 and hidden_states.dtype in (torch.bfloat16, torch.float16)
-                and self.config._attn_implementation == "tamd" and not kwargs.get("output_attentions", False)):
+                and self.config._attn_implementation == "tamd" and not kwargs.get("output_attentions", False)
+                and plain_weights(self.query, self.key, self.value)):
             note_fallback(self, hidden_states, "kv_cache" if past_key_values is not None else "unsupported")
             return super().forward(hidden_states, attention_mask=attention_mask, past_key_values=past_key_values,
                                    **kwargs)
@@ -68,7 +69,8 @@ class _DenseResidualLN:
                                          self.LayerNorm.eps, self.dropout.p)
 
     def _ok(self, x):
-        return _gpu(x) and x.dtype in (torch.bfloat16, torch.float16) and self.dense.bias is not None
+        return (_gpu(x) and x.dtype in (torch.bfloat16, torch.float16) and self.dense.bias is not None
+                and plain_weights(self.dense))
 
 
 class TamdBertSelfOutput(_DenseResidualLN, ref.BertSelfOutput):
@@ -97,7 +99,8 @@ class TamdBertIntermediate(ref.BertIntermediate):
     def forward(self, hidden_states):
         act = _act_name(self, "_tamd_act", self.intermediate_act_fn)
         if not (_gpu(hidden_states) and act in ops.ACT_CODES and ops.ACT_CODES[act] != ops.ACT_NONE
-                and hidden_states.dtype in (torch.bfloat16, torch.float16) and self.dense.bias is not None):
+                and hidden_states.dtype in (torch.bfloat16, torch.float16) and self.dense.bias is not None
+                and plain_weights(self.dense)):
             note_fallback(self, hidden_states)
             return super().forward(hidden_states)
         return ops.linear(hidden_states, self.dense.weight, self.dense.bias, act=ops.ACT_CODES[act])
@@ -119,6 +122,7 @@ class TamdBertLayer(ref.BertLayer):
                 and not kwargs.get("output_attentions", False) and sa.query.bias is not None
                 and so.dense.bias is not None and inter.dense.bias is not None and out.dense.bias is not None
                 and sa.query.weight.dtype == hidden_states.dtype
+                and plain_weights(sa.query, sa.key, sa.value, so.dense, inter.dense, out.dense)
                 and ops.ACT_CODES.get(_act_name(inter, "_tamd_act", inter.intermediate_act_fn), ops.ACT_NONE) != ops.ACT_NONE
                 and so.dropout.p == out.dropout.p
                 and not _has_hooks(att, sa, so, inter, out, so.LayerNorm, out.LayerNorm)

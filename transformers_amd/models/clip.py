@@ -10,7 +10,7 @@ from transformers.models.clip import modeling_clip as ref
 
 from .. import ops
 from ..fused_params import FusedWeights
-from .common import _gpu, _has_hooks, note_fallback
+from .common import _gpu, _has_hooks, note_fallback, plain_weights
 
 
 class TamdCLIPAttention(ref.CLIPAttention):
@@ -27,7 +27,8 @@ class TamdCLIPAttention(ref.CLIPAttention):
         d = self.head_dim
         if not (_gpu(hidden_states) and d in (64, 128) and hidden_states.dtype in (torch.bfloat16, torch.float16)
                 and self.config._attn_implementation == "tamd"
-                and not kwargs.get("output_attentions", False)):
+                and not kwargs.get("output_attentions", False)
+                and plain_weights(self.q_proj, self.k_proj, self.v_proj, self.out_proj)):
             note_fallback(self, hidden_states)
             return super().forward(hidden_states, attention_mask=attention_mask, **kwargs)
         b, s, h = hidden_states.shape
@@ -52,7 +53,8 @@ class TamdCLIPMLP(ref.CLIPMLP):
     def forward(self, hidden_states):
         act = self.config.hidden_act
         if not (_gpu(hidden_states) and isinstance(act, str) and ops.ACT_CODES.get(act, 0) != ops.ACT_NONE
-                and hidden_states.dtype in (torch.bfloat16, torch.float16) and self.fc1.bias is not None):
+                and hidden_states.dtype in (torch.bfloat16, torch.float16) and self.fc1.bias is not None
+                and plain_weights(self.fc1, self.fc2)):
             note_fallback(self, hidden_states)
             return super().forward(hidden_states)
         hmid = ops.linear(hidden_states, self.fc1.weight, self.fc1.bias, act=ops.ACT_CODES[act])

@@ -52,6 +52,14 @@ def fallback_calls(reset: bool = False) -> dict:
     return out
 
 
+def plain_weights(*linears) -> bool:
+    """False when one of `linears` holds one-byte weights (an FP8Linear of integrations/finegrained_fp8.py: e4m3 bytes with
+    block scales beside them).  A layer path that fuses such children's `.weight`, or hands it to a GEMM itself, would read
+    bytes as numbers: where a fusion is decided this is asked first, and the layer keeps the reference's forward -- whose
+    children, models/fp8.py among them, are called."""
+    return all(lin.weight.element_size() > 1 for lin in linears)
+
+
 class TamdLinear(nn.Linear):
     def forward(self, x):
         w = self.weight

@@ -21,7 +21,7 @@ from .. import layer_ops, ops
 from ..fused_params import FusedWeights
 
 
-from .common import _has_hooks, _placement_ok, note_fallback  # noqa: E402
+from .common import _has_hooks, _placement_ok, note_fallback, plain_weights  # noqa: E402
 
 
 def _on_gpu(t: torch.Tensor) -> bool:
@@ -51,7 +51,8 @@ class TamdLlamaMLP(ref.LlamaMLP):
         w = self.gate_proj.weight
         if (not _on_gpu(x) or self.config.hidden_act not in ("silu", "swish") or self.gate_proj.bias is not None
                 or self.down_proj.bias is not None or x.dtype not in (torch.bfloat16, torch.float16)
-                or w.dtype != x.dtype or w.shape[0] % 8 or w.shape[1] % 8):
+                or w.dtype != x.dtype or w.shape[0] % 8 or w.shape[1] % 8
+                or not plain_weights(self.up_proj, self.down_proj)):
             note_fallback(self, x)
             return super().forward(x)
         gu = self._fused().linear(x)
@@ -72,7 +73,8 @@ class TamdLlamaAttention(ref.LlamaAttention):
     def _fast_ok(self, hidden_states, past_key_values) -> bool:
         return (_on_gpu(hidden_states) and past_key_values is None and self.q_proj.bias is None
                 and self.head_dim in (64, 128) and hidden_states.dtype in (torch.bfloat16, torch.float16)
-                and self.config._attn_implementation == "tamd")
+                and self.config._attn_implementation == "tamd"
+                and plain_weights(self.q_proj, self.k_proj, self.v_proj, self.o_proj))
 
     def _cached_ok(self, hidden_states) -> bool:
         """A forward with a KV cache (prefill into it, or a decode step) on the kernels: inference only."""
@@ -137,7 +139,7 @@ class TamdLlamaDecoderLayer(ref.LlamaDecoderLayer):
                 and attn._fast_ok(hidden_states, past_key_values)
                 and not (attn.training and attn.attention_dropout > 0)  # the per-module path carries dropout
                 and mlp.config.hidden_act in ("silu", "swish") and mlp.gate_proj.bias is None
-                and attn.o_proj.bias is None
+                and attn.o_proj.bias is None and plain_weights(mlp.gate_proj, mlp.up_proj, mlp.down_proj)
                 and not _has_hooks(attn, mlp, self.input_layernorm, self.post_attention_layernorm)
                 and _placement_ok(self, hidden_states.device, attn.q_proj.weight, mlp.down_proj.weight))
 
@@ -145,7 +147,7 @@ class TamdLlamaDecoderLayer(ref.LlamaDecoderLayer):
         attn, mlp = self.self_attn, self.mlp
         return (isinstance(attn, TamdLlamaAttention) and isinstance(mlp, TamdLlamaMLP) and attn._cached_ok(hidden_states)
                 and mlp.config.hidden_act in ("silu", "swish") and mlp.gate_proj.bias is None and mlp.down_proj.bias is None
-                and mlp.gate_proj.weight.dtype == hidden_states.dtype
+                and mlp.gate_proj.weight.dtype == hidden_states.dtype and plain_weights(mlp.up_proj, mlp.down_proj)
                 and not _has_hooks(attn, mlp, self.input_layernorm, self.post_attention_layernorm)
                 # (the cached path reads the children's weights directly: an accelerate `device_map` / offload wrapper on a
                 # child would not run -- ADVICE r4; such layers take the reference module, whose children are called)

@@ -822,6 +822,9 @@ register("moe_experts_bwd", _moe_experts_bwd_fake)
 register("moe_experts", _moe_experts_fake, _moe_experts_backward, _moe_experts_setup)
 # the decode-step experts (csrc/gemv_moe.inc): forward only, no autograd formula
 register("moe_experts_decode", lambda x, top_k_index, top_k_weights, gate_up, down: x.new_empty(x.shape[0], x.shape[1]))
+# nn.Linear over FP8 block-scaled weights (csrc/gemv_fp8.inc): forward only, no autograd formula -- the op refuses an input that
+# requires grad by name
+register("linear_fp8w", lambda x, w8, scale_inv, bias=None: x.new_empty(*x.shape[:-1], w8.shape[0]))
 
 
 # The router in front of them (MixtralTopKRouter.forward / Qwen3MoeTopKRouter.forward behind their gate product; csrc/moe_router.inc):
@@ -1186,6 +1189,21 @@ def moe_experts(x, top_k_index, top_k_weights, gate_up_proj, down_proj):
         _moe_decode_calls += 1
         return T.moe_experts_decode(x, top_k_index, top_k_weights, gate_up_proj, down_proj)
     return T.moe_experts(x, top_k_index, top_k_weights, gate_up_proj, down_proj, train)[0]
+
+
+FP8_BLOCK = 128  # (include/tamd.h tamd_gemm_fp8w: the scale block, rows and columns)
+
+
+def linear_fp8w_supported(rows: int, n: int, k: int) -> bool:
+    """Shapes torch.ops.tamd.linear_fp8w takes: K in whole 16-byte loads; past 16 rows the GEMM kernels' N % 8 == 0."""
+    return rows > 0 and k % 16 == 0 and (rows <= 16 or n % 8 == 0)
+
+
+def linear_fp8w(x, w8, scale_inv, bias=None):
+    """x [.., K] (bf16 / fp16) against w8 [N, K] float8_e4m3fn with scale_inv [ceil(N / 128), ceil(K / 128)] fp32 (one scale per
+    128 x 128 block) -> [.., N].  W8A16, inference only (include/tamd.h tamd_gemm_fp8w): up to 16 rows stream the weight bytes
+    once, more rows dequantise row chunks in front of the GEMM kernels."""
+    return T.linear_fp8w(x, w8, scale_inv, bias)
 
 
 ROUTER_MAX_TOP_K = 16  # (include/tamd.h tamd_moe_router_fwd)

@@ -16,7 +16,7 @@ from torch import nn
 from . import attention, experts
 
 
-def _tables(moe_router: bool = True) -> Dict[Type[nn.Module], Type[nn.Module]]:
+def _tables(moe_router: bool = True, fp8_linear: bool = True) -> Dict[Type[nn.Module], Type[nn.Module]]:
     from .models import bert, clip, common, gpt2, llama
 
     table: Dict[Type[nn.Module], Type[nn.Module]] = {}
@@ -25,7 +25,24 @@ def _tables(moe_router: bool = True) -> Dict[Type[nn.Module], Type[nn.Module]]:
     moe = _moe() if moe_router else None
     if moe is not None:
         table.update(moe.REPLACEMENTS)
+    fp8 = _fp8() if fp8_linear else None
+    if fp8 is not None:
+        table.update(fp8.REPLACEMENTS)
     return table
+
+
+def _fp8():
+    """models/fp8.py, or None with a reference that has no integrations/finegrained_fp8.py (no FP8Linear to subclass).  Only
+    that import is guarded: an error inside the project's own module is raised."""
+    import importlib
+
+    try:
+        importlib.import_module("transformers.integrations.finegrained_fp8")
+    except ImportError:
+        return None
+    from .models import fp8
+
+    return fp8
 
 
 _MOE_MISSING = False
@@ -54,7 +71,8 @@ def _moe():
 
 
 def accelerate(model: nn.Module, attn_implementation: bool = True, fuse_loss: bool = True,
-               fused_lm_head_loss: bool = False, experts_implementation: bool = True, moe_router: bool = True) -> nn.Module:
+               fused_lm_head_loss: bool = False, experts_implementation: bool = True, moe_router: bool = True,
+               fp8_linear: bool = True) -> nn.Module:
     """Switch `model` (any PreTrainedModel containing Llama / BERT / CLIP / GPT-2 blocks) to the MI355X path.
 
     * registers and selects `attn_implementation="tamd"` (reference API: `set_attn_implementation`,
@@ -65,6 +83,8 @@ def accelerate(model: nn.Module, attn_implementation: bool = True, fuse_loss: bo
     * swaps norm / MLP / attention / layer modules for their tamd subclasses in place, and -- unless `moe_router=False` (the
       A/B switch) -- the softmax + top-k routers of Mixtral / Qwen2-MoE / Qwen3-MoE / OLMoE blocks and the sigmoid, group-limited
       routers of DeepSeek-V3 / GLM-4-MoE and their copies (models/moe.py);
+    * unless `fp8_linear=False` (the A/B switch), swaps the `FP8Linear` modules of an FP8 block-scaled checkpoint (DeepSeek-V3 / R1,
+      Qwen3-FP8, GLM-FP8: integrations/finegrained_fp8.py) for models/fp8.py -- W8A16 on the weight-streaming kernel, inference only;
     * installs the fused cross-entropy as `model.loss_function` for causal-LM heads
       (reference hook: modeling_utils.py:4652-4669);
     * `fused_lm_head_loss=True` (opt-in, Llama): training forwards with labels run the lm_head GEMM and the loss chunk by
@@ -73,7 +93,7 @@ def accelerate(model: nn.Module, attn_implementation: bool = True, fuse_loss: bo
     """
     attention.register()
     experts.register()
-    table = _tables(moe_router)
+    table = _tables(moe_router, fp8_linear)
     n = 0
     for m in model.modules():
         repl = table.get(type(m))
@@ -127,7 +147,7 @@ def accelerate(model: nn.Module, attn_implementation: bool = True, fuse_loss: bo
     # eager weight fusion (before DDP wraps the model)
     for m in model.modules():
         fuse = getattr(m, "_fused", None)
-        if callable(fuse) and all(p.is_cuda for p in m.parameters(recurse=True)):
+        if callable(fuse) and all(p.is_cuda and p.element_size() > 1 for p in m.parameters(recurse=True)):  # (no FP8Linear child)
             fuse().weight()
         pad = getattr(m, "_padded", None)
         if callable(pad) and all(p.is_cuda for p in m.parameters(recurse=True)):
