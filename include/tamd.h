@@ -410,10 +410,15 @@ int tamd_moe_gemv_down(const void* act, const int64_t* top_k_index, const void* 
  *   M <= 16   Y[m, n] = rT( sum_k X[m, k] * (f32(W8[n, k]) * S[n / 128, k / 128]) [+ bias[n]] ), accumulated in fp32; the
  *             dequantised weight is never rounded to T.  One launch that streams W8 once: HBM traffic N K + 4 |S| + M (K + N)
  *             sizeof(T) bytes.  (Per lane and step the 16 products of one scale block are summed unscaled and enter the
- *             accumulator as fma(scale, partial, acc): the result differs from the expression above by fp32 summation error.)
- *   M  > 16   Wd = rT( r32( f32(W8) * S ) ), then Y = tamd_gemm(X, Wd, bias, R) with that kernel's documented roundings.  Wd is
- *             built in chunks of whole scale rows inside `workspace`: chunk_bytes caps a chunk (0: 64 MiB; never less than 128
- *             rows), tamd_gemm_fp8w_workspace_bytes(M, N, K, chunk_bytes) is the size to pass (0 for M <= 16).
+ *             accumulator as fma(scale, partial, acc): the result differs from the expression above by fp32 summation error.
+ *             One row, two rows, and three or four rows below 4096 weight rows run on the VALU; the other shapes run the same
+ *             stream on 16x16x32 MFMAs over the unscaled weights, one fma(scale, partial, acc) per 128-wide scale block.)
+ *   M  > 16   Wd = rT( r32( f32(W8) * S ) ), then Y = X . Wd^T accumulated in fp32 with tamd_gemm's documented roundings.
+ *             17 <= M <= 64: one launch that streams W8 once and builds the same Wd, bit for bit, in registers in front of the
+ *             MFMAs (HBM traffic as above); the workspace is validated as below and then NOT written.
+ *             M > 64: Wd is built in chunks of whole scale rows inside `workspace` and each chunk goes through tamd_gemm:
+ *             chunk_bytes caps a chunk (0: 64 MiB; never less than 128 rows).
+ *             tamd_gemm_fp8w_workspace_bytes(M, N, K, chunk_bytes) is the size to pass for every M > 16 (0 for M <= 16).
  * The two forms differ by ONE rounding of every weight to T.
  * Refusals, before any launch and with every output untouched: TAMD_E_DTYPE for any dtype but bf16 / f16; TAMD_E_SHAPE for a
  * non-positive dimension, K % 16 != 0, a leading dimension below its width, and -- M > 16 only -- N % 8 != 0 or ldy % 8 != 0;

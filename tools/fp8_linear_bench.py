@@ -1,6 +1,9 @@
 """FP8 block-scaled linear (torch.ops.tamd.linear_fp8w: csrc/gemv_fp8.inc) against this project's bf16 product on the same N, K
 (ops.linear: csrc/gemv.hip at M <= 16, the GEMM kernels above) -- the yardstick: the streaming form reads half the bytes -- and,
-with --reference where its Triton path runs on the box, the reference's FP8Linear.forward.  DeepSeek-V3 dense shapes at M = 1, 8, 16, 512.
+with --reference where its Triton path runs on the box, the reference's FP8Linear.forward.  DeepSeek-V3 dense shapes at M = 1, 2, 4,
+8, 16, 32, 64, 512.  The ops run through libtamd_diag.so, whose TAMD_FP8W_MFMA switch (csrc/gemv_fp8.inc, read at every call) gives
+the arm `fp8w_before`: every M as it ran before gemv_fp8w_mfma_kernel (the streaming kernel up to 16 rows, dequantise + GEMM
+above); at 2 and 4 rows, where the dispatch rule chooses per shape, `fp8w_mfma` forces the new kernel.  `fp8w` is the product's rule.
 
 Every arm walks a ring of weight copies larger than the 256 MB of last-level cache, so each launch streams its weights from HBM;
 the arms alternate inside one process; one JSON line per point, appended to --out when given.  Times are per call (device events
@@ -11,13 +14,17 @@ kernel time.
 """
 import argparse
 import json
+import os
 import sys
 from pathlib import Path
 
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+import _diag  # noqa: E402
 from transformers_amd import ops  # noqa: E402
+
+_diag.use_diag()
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=5)
@@ -28,16 +35,21 @@ ap.add_argument("--reference", action="store_true",
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 SHAPES = [(7168, 1536), (7168, 576), (1536, 24576), (16384, 7168), (7168, 18432), (18432, 7168)]  # K -> N
-ROWS = [1, 8, 16, 512]
+ROWS = [1, 2, 4, 8, 16, 32, 64, 512]
+SWITCH = {"fp8w_before": "0", "fp8w_mfma": "2"}  # TAMD_FP8W_MFMA of an arm (any other arm: unset, the product's rule)
 
 
-def timed(fn, iters):
+def timed(arm, fn, iters):
+    os.environ.pop("TAMD_FP8W_MFMA", None)
+    if arm in SWITCH:
+        os.environ["TAMD_FP8W_MFMA"] = SWITCH[arm]
     st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     st.record()
     for i in range(iters):
         fn(i)
     en.record()
     torch.cuda.synchronize()
+    os.environ.pop("TAMD_FP8W_MFMA", None)
     return st.elapsed_time(en) / iters
 
 
@@ -61,8 +73,10 @@ for k, n in SHAPES:
           for w, s in zip(wb, sc)]
     for m in ROWS:
         x = torch.randn(m, k, device=dev).bfloat16()
-        arms = {"fp8w": lambda i: ops.linear_fp8w(x, w8[i % ring], sc[i % ring]),
-                "bf16": lambda i: ops.linear(x, wb[i % ring])}
+        fp8w = lambda i: ops.linear_fp8w(x, w8[i % ring], sc[i % ring])  # noqa: E731
+        arms = {"fp8w": fp8w, "fp8w_before": fp8w, "bf16": lambda i: ops.linear(x, wb[i % ring])}
+        if m in (2, 4):
+            arms["fp8w_mfma"] = fp8w
         if reference_state in (None, True):
             mods = [reference_module(w, s) for w, s in zip(w8, sc)]
             try:
@@ -75,20 +89,24 @@ for k, n in SHAPES:
                 reference_state = f"{type(e).__name__}: {str(e)[:160]}"
         with torch.no_grad():
             y, yb = arms["fp8w"](0).float(), arms["bf16"](0).float()
-            slowest = max(timed(fn, 5) for fn in arms.values())
+            os.environ["TAMD_FP8W_MFMA"] = "0"
+            yo = fp8w(0).float()  # (the same operands through the code as it was: fp32 summation order apart, the same values)
+            slowest = max(timed(a, fn, 5) for a, fn in arms.items())
             iters = max(10, min(20000, int(250.0 / max(slowest, 1e-3))))  # a timed window of ~250 ms of the slowest arm
-            for fn in arms.values():
-                timed(fn, 3)
+            for a, fn in arms.items():
+                timed(a, fn, 3)
             ms = {a: [] for a in arms}
             for _ in range(args.rounds):  # alternating
                 for a, fn in arms.items():
-                    ms[a].append(timed(fn, iters))
+                    ms[a].append(timed(a, fn, iters))
         med = {a: sorted(v)[len(v) // 2] for a, v in ms.items()}
-        nbytes = {"fp8w": n * k + 4 * sc[0].numel() + m * (k + n) * 2, "bf16": 2 * n * k + m * (k + n) * 2}
+        nbytes = {a: n * k + 4 * sc[0].numel() + m * (k + n) * 2 for a in arms if a.startswith("fp8w")}
+        nbytes["bf16"] = 2 * n * k + m * (k + n) * 2
         rec = {"K": k, "N": n, "M": m, "ring": ring, "iters": iters, "rel_diff_fp8w_vs_bf16_product": round(float((y - yb).norm() / yb.norm()), 4),
+               "rel_diff_fp8w_vs_before": float(f"{float((y - yo).norm() / yo.norm()):.3g}"),
                **{f"{a}_ms": [round(v, 4) for v in ms[a]] for a in arms}, **{f"{a}_median_ms": round(med[a], 4) for a in arms},
                **{f"{a}_TBps": round(nbytes[a] / (med[a] * 1e-3) / 1e12, 3) for a in nbytes},
-               "fp8w_over_bf16": round(med["fp8w"] / med["bf16"], 3),
+               "fp8w_over_bf16": round(med["fp8w"] / med["bf16"], 3), "fp8w_over_before": round(med["fp8w"] / med["fp8w_before"], 3),
                "reference_fp8linear": "timed" if reference_state is True else f"not run ({reference_state})", "clock_probe": "not run"}
         line = json.dumps(rec)
         print(line, flush=True)
