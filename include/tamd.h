@@ -416,8 +416,11 @@ int tamd_moe_gemv_down(const void* act, const int64_t* top_k_index, const void* 
  *   M  > 16   Wd = rT( r32( f32(W8) * S ) ), then Y = X . Wd^T accumulated in fp32 with tamd_gemm's documented roundings.
  *             17 <= M <= 64: one launch that streams W8 once and builds the same Wd, bit for bit, in registers in front of the
  *             MFMAs (HBM traffic as above); the workspace is validated as below and then NOT written.
- *             M > 64: Wd is built in chunks of whole scale rows inside `workspace` and each chunk goes through tamd_gemm:
- *             chunk_bytes caps a chunk (0: 64 MiB; never less than 128 rows).
+ *             64 < M <= 1024: the same in one launch of a tile kernel (csrc/gemm_fp8w.inc: 128 weight rows x 64 or 128 rows of X
+ *             per workgroup, X through LDS, Wd built in registers): the workspace is validated and NOT written either.
+ *             M > 1024 (where the tile kernel measured slower), or a 128-row tile of X that spans 2 GiB or more (ldx >= 2^23):
+ *             Wd is built in chunks of whole scale rows inside `workspace` and each chunk goes through tamd_gemm: chunk_bytes
+ *             caps a chunk (0: 64 MiB; never less than 128 rows).
  *             tamd_gemm_fp8w_workspace_bytes(M, N, K, chunk_bytes) is the size to pass for every M > 16 (0 for M <= 16).
  * The two forms differ by ONE rounding of every weight to T.
  * Refusals, before any launch and with every output untouched: TAMD_E_DTYPE for any dtype but bf16 / f16; TAMD_E_SHAPE for a

@@ -7,7 +7,9 @@
 //            false> for the rest (fp8w_use_mfma records the measurement behind the rule)
 //   M  > 16  Wd = rT(r32(f32(W8) * S)), Y = X . Wd^T with the GEMM kernels' roundings:
 //            17 .. 64 rows: gemv_fp8w_mfma_kernel<ROUNDW = true> builds Wd in registers, one launch, the workspace is not written;
-//            above: dequant_fp8w_kernel + tamd_gemm per row chunk
+//            65 .. 1024 rows: gemm_fp8w_kernel (gemm_fp8w.inc), the same in 128-row W tiles with X in LDS: one launch, no workspace
+//            write; above (fp8w_use_tile holds the measurements): dequant_fp8w_kernel + tamd_gemm per row chunk, which is also the
+//            diagnostic "before" arm
 //
 // gemv_fp8w_kernel keeps gemv_kernel's split -- one wave owns R consecutive weight rows, four waves per workgroup, no LDS, no
 // MFMA, a reduction over the lanes at the end -- on a data path of its own:
@@ -30,7 +32,7 @@
 namespace tamd {
 
 constexpr int kFp8Block = 128;                             // the scale block (rows and columns)
-constexpr size_t kFp8ChunkBytes = (size_t)64 << 20;        // default cap of the dequantised chunk (M > 64)
+constexpr size_t kFp8ChunkBytes = (size_t)64 << 20;        // default cap of the dequantised chunk (M > 16)
 constexpr int kFp8MfmaMaxRows = 64;                        // rows of X up to which gemv_fp8w_mfma_kernel runs
 
 struct GemvFp8Args {
@@ -428,6 +430,8 @@ static int64_t fp8w_chunk_rows(int64_t N, int64_t K, size_t chunk_bytes) {
 
 }  // namespace tamd
 
+#include "gemm_fp8w.inc"
+
 using namespace tamd;
 
 extern "C" {
@@ -476,6 +480,10 @@ int tamd_gemm_fp8w(const void* X, const void* W8, const float* S, void* Y, const
   }
   const int64_t chunk = fp8w_chunk_rows(N, K, chunk_bytes);
   if (!workspace || !aligned16(workspace) || workspace_bytes < (size_t)chunk * (size_t)K * 2) return TAMD_E_ARG;
+  if (fp8w_use_tile(M, ldx)) {  // 65 .. 1024 rows: Wd in registers in front of the tile kernel's MFMAs; the workspace is not touched
+    TAMD_DISPATCH_HALF(dtype, return (gemm_fp8w_launch<T>(g, epilogue, s)));
+    return TAMD_E_DTYPE;
+  }
   if (mfma) {  // 17 .. 64 rows: the same Wd in registers, one launch; the workspace is validated and not touched
     TAMD_DISPATCH_HALF(dtype, return (gemv_fp8w_mfma_launch<T>(g, epilogue, s)));
     return TAMD_E_DTYPE;

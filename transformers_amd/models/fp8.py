@@ -5,8 +5,9 @@ DeepSeek-V3 / R1, Qwen3-FP8 and GLM-FP8 checkpoints load their dense projections
 The reference's forward quantises the activations per 128 values and calls a Triton kernel.  Here the activations stay
 bf16 / fp16 (W8A16, include/tamd.h tamd_gemm_fp8w): a decode step streams the weight bytes once -- half the bytes of a bf16
 projection, which is what such a step is bound by.  Up to 64 rows (a batch of sequences, a block of speculative tokens, a short
-second turn) the same single launch streams the bytes through the matrix pipe, dequantising in registers; more rows dequantise
-row chunks in front of the GEMM kernels.
+second turn) the same single launch streams the bytes through the matrix pipe, dequantising in registers; up to 1024 rows (a
+prefill) one fused tile kernel keeps X in LDS and dequantises each weight byte once per workgroup, again in registers; more rows
+dequantise row chunks in front of the GEMM kernels.
 That is closer to the exact product than the reference's forward and NOT bit-identical to it.
 
 Served: one-byte e4m3 weights, block_size (128, 128), activation_scheme "dynamic", fp32 scales, bf16 / fp16 inputs on the

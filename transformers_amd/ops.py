@@ -1203,8 +1203,9 @@ def linear_fp8w(x, w8, scale_inv, bias=None):
     """x [.., K] (bf16 / fp16) against w8 [N, K] float8_e4m3fn with scale_inv [ceil(N / 128), ceil(K / 128)] fp32 (one scale per
     128 x 128 block) -> [.., N].  W8A16, inference only (include/tamd.h tamd_gemm_fp8w): up to 64 rows stream the weight bytes
     once (on the VALU at one and two rows and at 3 .. 4 rows of a small N, through 16x16x32 MFMAs otherwise; from 17 rows on the
-    weight is rounded to the activations' type in registers, as the GEMM form does), more rows dequantise row chunks in front of
-    the GEMM kernels."""
+    weight is rounded to the activations' type in registers, as the GEMM form does), 65 .. 1024 rows run one fused tile kernel
+    (csrc/gemm_fp8w.inc: X through LDS, the same rounded weight built in registers in front of the MFMAs), more rows dequantise
+    row chunks in front of the GEMM kernels."""
     return T.linear_fp8w(x, w8, scale_inv, bias)
 
 
